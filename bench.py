@@ -21,9 +21,13 @@ all-reduce + optimizer kernels follow it on the stream) and replayed.  TTTS_GRAP
 Other configs: --config scaled --batch 32 (BASELINE configs[4] per-GPU shard), --batch 16 (configs[1] shape, fp32).
 --ragged --cycle N: a stream of N differently shaped LJSpeech-like batches, round-robin (one graph per shape out of the
 shape-keyed cache; --lattice P,M rounds the padded lengths to multiples of P phonemes / M frames first).
-After the timed steps the same step is replayed for --sustain seconds more and the median step time of that stretch is
-reported as `sustained` (the timed region of a default run is a third of a second: too short to show the clocks the chip
-holds under sustained matrix load).
+A plain run sets up, warms up, times --steps steps and prints the result line; nothing else.  --full adds the other figures:
+after the timed steps one instrumented eager step (`roofline`: the dominant GEMM kernel against its ceilings), the same
+step replayed for --sustain seconds more with the median step time of that stretch reported as `sustained` (the timed
+region of a default run is a third of a second: too short to show the clocks the chip holds under sustained matrix load),
+the step with the other setting of the attention maps, and the CPU oracle's rate (`cpu_baseline`).
+--dump-outputs DIR writes what the last timed step produced (loss, parameters after the update, a fixed sample of the
+gradients, BatchNorm running statistics) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -352,6 +356,44 @@ def launch_check(args, world: int, rank: int):
         dist.destroy_process_group()
 
 
+DUMP_FULL_MAX = 10_000_000       # parameters: written whole up to this many values (40 MB), else a fixed sample of this size
+DUMP_SAMPLE = 1 << 21            # gradients: a fixed sample of this many values (8 MB)
+
+
+def _fixed_sample(x: torch.Tensor, n: int, seed: int) -> torch.Tensor:
+    """`x` (1-D) itself if it holds at most n values, else n of them at sorted positions drawn from a seeded CPU generator"""
+    if x.numel() <= n:
+        return x
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(x.numel(), generator=g)[:n].sort().values
+    return x[idx.to(x.device)]
+
+
+def dump_outputs(lm, loss: torch.Tensor, out_dir: str) -> dict:
+    """What a caller of the timed step holds after its last step, as float32 .npy files in `out_dir`: the step's loss, every
+    trainable parameter after the optimizer update (model order, flattened and concatenated), their gradients of that step
+    (a fixed sample) and the BatchNorm running statistics.  -> {name: shape}"""
+    import numpy as np
+    torch.cuda.synchronize()
+    model = lm.model
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+    stats = [b.detach().reshape(-1).float() for n, b in model.named_buffers() if "running_" in n and b.is_floating_point()]
+    arrays = {"loss": loss.detach().reshape(1),
+              "params": _fixed_sample(flat_p, DUMP_FULL_MAX, 1),
+              "grads": _fixed_sample(flat_g, DUMP_SAMPLE, 2)}
+    if stats:
+        arrays["bn_running_stats"] = torch.cat(stats)
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def workload_name(args) -> str:
     if args.config == "base" and args.batch == 64:
         return "BASELINE configs[2] (batch 64, 1 GPU; per-GPU shard of configs[3])"
@@ -374,7 +416,7 @@ def main():
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true")
-    ap.add_argument("--gemm-shapes", action="store_true", help="print the instrumented step's per-shape GEMM table to stderr")
+    ap.add_argument("--gemm-shapes", action="store_true", help="with --full: print the instrumented step's per-shape GEMM table to stderr")
     ap.add_argument("--cycle", type=int, default=1, help="number of distinct ragged batch shapes fed round-robin")
     ap.add_argument("--lattice", default="", help="P,M: pad batches to multiples of P phonemes / M frames (graph-cache key)")
     ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer step (train.py:42 uses 4)")
@@ -414,7 +456,13 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="exercise the launcher protocol only (process group, barrier, MAX-over-ranks clock, rank-0 JSON line) "
                          "over gloo on the host: no model, no GPU, not a measurement")
-    ap.add_argument("--sustain", type=float, default=float(os.environ.get("TTTS_BENCH_SUSTAIN", "10")), help="seconds of further replays after the timed steps (0: skip)")
+    ap.add_argument("--sustain", type=float, default=float(os.environ.get("TTTS_BENCH_SUSTAIN", "10")),
+                    help="with --full: seconds of further replays after the timed steps (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the figures beyond the headline: roofline probe, sustained stretch, the other attention-map "
+                         "setting, CPU baseline (each can still be left out with its --no-* / --sustain 0 switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step produced as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -567,9 +615,13 @@ def main():
     elapsed = float(t.item())
     frames_all, flops_all = float(tot[0].item()), float(tot[1].item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(lm, loss, args.dump_outputs)
+        note(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
 
     probe = None
-    if not args.no_probe:
+    probe_step = args.full and not args.no_probe
+    if probe_step:
         # one extra, untimed step on EVERY rank (it contains the gradient all-reduce); rank 0 instruments it
         # (taken right behind the timed steps, BEFORE the sustained stretch: the kernel's clock then is the timed region's, not that
         # of a chip ten seconds into a soak -- round 5's probe read 108 us per launch where the step's own launches took 98)
@@ -585,11 +637,11 @@ def main():
         else:
             step(args.warmup + args.steps)
     fence()
-    if not args.no_probe:
+    if probe_step:
         ts.use_graph = graph_was                 # the sustained stretch replays the graphs again
     # sustained figure: keep stepping for args.sustain seconds, in stretches of `args.steps` steps fenced like the timed ones
     sustained = None
-    if args.sustain > 0 and not rehearsal:
+    if args.full and args.sustain > 0 and not rehearsal:
         stretch, t_s0, k = [], time.perf_counter(), args.warmup + args.steps
         while True:
             fence()
@@ -617,7 +669,7 @@ def main():
     # step WRITES them, as the reference does (`config.alignments_written`); the secondary figure is the step that skips the
     # maps nobody reads.
     with_alignments = None
-    if (not args.no_alignments_figure and world == 1 and not cycling and args.accumulate == 1
+    if (args.full and not args.no_alignments_figure and world == 1 and not cycling and args.accumulate == 1
             and use_graph and not rehearsal):
         lm.config["training"]["train_step_alignments"] = not args.alignments
         ts2 = TrainStep(lm, optimizer, scheduler, batch, graph=True, seed=42 + rank, eager_warmup=2)
@@ -726,7 +778,7 @@ def main():
                                                    "bytes_are": "per output tile (256 x 256; 128 x 256 for gemm_h3i): activation block + weight block loaded, output stored",
                                                    "peak_is": "256 CUs x ~10 B/cycle/CU x 2.4 GHz (global_load_dwordx4, HBM-bound); L2 hits can exceed it"}
             out["roofline"]["gemm_kernels"] = probe["all"]
-        if not args.no_cpu_baseline and world == 1:          # (rank 0 at N = 1 only: the other ranks would wait for it)
+        if args.full and not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: the other ranks would wait for it)
             out["cpu_baseline"] = cpu_baseline(cfg, args.tp, args.config)
         print(json.dumps(out), flush=True)
     if world > 1 or dist.is_initialized():

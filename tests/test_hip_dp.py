@@ -194,8 +194,9 @@ def test_bench_runs_under_a_one_rank_rccl_group():
     s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", TTTS_FORCE_DIST="1")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "6", "--warmup", "3", "--sustain", "0", "--batch", "16",
-                        "--no-cpu-baseline", "--no-alignments-figure"], env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "6", "--warmup", "3", "--sustain", "0",
+                        "--batch", "16", "--no-cpu-baseline", "--no-alignments-figure"], env=env, capture_output=True, text=True, timeout=900,
+                       cwd=REPO)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["config"]["process_group"].startswith("nccl")
