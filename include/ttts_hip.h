@@ -53,6 +53,20 @@ typedef struct ttts_step_state {
     int64_t reserved; /* 24 */
 } ttts_step_state;
 
+/* Per-frame scalars of autoregressive decoding (32 bytes, fields at fixed offsets), read by every ttts_decode_* kernel when it
+ * runs: one captured graph of a chunk of frames then serves every frame, every max_len up to the buffers' capacity and every
+ * threshold.  The caller resets it with one small host-to-device copy per call: t = 1, t_end = max_len (the buffers hold
+ * t_end rows of frames), stop_frame = -1.  ttts_decode_frame_out records the first frame at which every row's stop
+ * probability reaches the threshold in stop_frame, then advances t.  Every decode kernel returns at once when
+ * t >= t_end or stop_frame >= 0. */
+typedef struct ttts_decode_state {
+    int64_t t;            /*  0: the frame being decoded (1-based: frame t is written to ys[:, t], frame 0 is the go frame) */
+    int64_t t_end;        /*  8: max_len */
+    int64_t stop_frame;   /* 16: first all-stop frame, -1 until one occurs */
+    float stop_threshold; /* 24: stop when sigmoid(stop logit) >= threshold for every row */
+    int32_t reserved;     /* 28 */
+} ttts_decode_state;
+
 const char* ttts_last_error(void);
 int ttts_abi_version(void);
 
@@ -495,6 +509,52 @@ int ttts_grad_norm(const float* g, float* norm_out, float* ws, size_t ws_bytes, 
 int ttts_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, const float* grad_norm, int64_t n, float lr,
                    float beta1, float beta2, float eps, int64_t step, float max_grad_norm, const ttts_step_state* st,
                    void* stream);
+
+/* ------------------------------------------------------------------ autoregressive decoding (one frame, M = B rows)
+ * The K/V-cache loop of TransformerTTS.inference (transformertts_amd/model/model.py:310-338; the reference's loop is
+ * model/model.py:354-384) as weight-streaming fp32 kernels whose frame index, length, threshold and stop
+ * state come from `st` (ttts_decode_state above).  Plain fp32 FMA arithmetic, fixed summation orders that depend on neither
+ * the row count nor the capacities (bitwise reproducible), no atomics.  Row strides are in floats; "(t - 1) * tstride" terms
+ * use the t read from `st`.
+ *
+ * y = act(x . w^T + bias) (+ residual): the decoder's in / out projections, FFN linears and the cross-attention q projection
+ * (torch/nn/functional.py in_proj / out_proj, torch/nn/modules/transformer.py _ff_block, model/layers.py:47-50 residuals).
+ * Row m of x is x + m * ldx + (t - 1) * x_tstride; w is (N, K) in its state-dict layout (row slices of a packed in-projection
+ * included); output column n < n_split goes to y + m * ldy + (t - 1) * y_tstride + n, column n >= n_split to
+ * y2 + m * ldy2 + (t - 1) * y2_tstride + (n - n_split) -- the K/V columns of a self-attention in-projection written straight
+ * into row t - 1 of that layer's cache.  K % 4 == 0, K <= 4096, x and w 16-byte aligned, ldx and x_tstride multiples of 4;
+ * act NONE or RELU; bias, residual may be NULL; y2 may be NULL when n_split == N. */
+int ttts_decode_linear(const float* x, int64_t ldx, int64_t x_tstride, const float* w, const float* bias, const float* residual,
+                       int64_t ldr, float* y, int64_t ldy, int64_t y_tstride, float* y2, int64_t ldy2, int64_t y2_tstride,
+                       int n_split, int M, int N, int K, int act, const ttts_decode_state* st, void* stream);
+/* Frame in: out[B,d] = relu(relu(ys[:, t-1] . w1^T + b1) . w2^T + b2) + alpha[0] * pe[t - 1]: the decoder pre-net in eval mode
+ * and the positional encoding of the newest frame (model/model.py:356-357 DecoderPreNet + PositionalEncoding, eval: no
+ * dropout).  ys is (B, t_end, n_mels) with batch stride ld_ys; pe is the (rows, d) table; tmp is B x d floats of scratch
+ * (16-byte aligned).  d and n_mels multiples of 4. */
+int ttts_decode_frame_in(const float* ys, int64_t ld_ys, int n_mels, const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* pe, const float* alpha, float* tmp, float* out, int B, int d,
+                         const ttts_decode_state* st, void* stream);
+/* Frame out: the heads (model/model.py:372-373 linear1 / linear2 on the last frame): ys[:, t] = x . w_mel^T + b_mel,
+ * stop[b * ld_stop + t - 1] = x . w_stop + b_stop; then, when every row has 1 / (1 + expf(-stop)) >= st->stop_threshold
+ * (torch.sigmoid(stop) >= threshold, model/model.py:379-380), st->stop_frame = t; finally st->t = t + 1. */
+int ttts_decode_frame_out(const float* x, const float* w_mel, const float* b_mel, const float* w_stop, const float* b_stop,
+                          float* ys, int64_t ld_ys, float* stop, int64_t ld_stop, int B, int d, int n_mels,
+                          ttts_decode_state* st, void* stream);
+/* y[M,d] = LayerNorm(x) (norm1 / norm2 / norm3 of the post-norm decoder layer, model/layers.py:46-50); d <= 1024 */
+int ttts_decode_layernorm(const float* x, const float* gamma, const float* beta, float* y, int M, int d, float eps,
+                          const ttts_decode_state* st, void* stream);
+/* One query row per (utterance b, head h) against key rows 0 .. len - 1 (scaled dot-product attention of torch's MHA,
+ * torch/nn/functional.py multi_head_attention_forward, q scaled by 1 / sqrt(head_dim)):
+ *   q row b at q + b * ldq, head h at column h * head_dim; key / value row j of utterance b at k / v + b * ld_batch + j * ld_row
+ *   (+ h * head_dim); len = lens[b] (int64, device; the memory key-padding mask of cross-attention) or, lens == NULL, the t of
+ *   `st` (self-attention over the cache rows written so far); len is clamped to max_keys.  Keys at or past len are never read.
+ *   out row b at out + b * ldo.  head_dim a multiple of 16 up to 128.
+ * Keys are split in blocks of 64 whose partials go to the caller's workspace (ttts_decode_attention_workspace_bytes) and are
+ * combined in block order by a second launch. */
+size_t ttts_decode_attention_workspace_bytes(int B, int H, int head_dim, int max_keys);
+int ttts_decode_attention(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
+                          const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
+                          int max_keys, const ttts_decode_state* st, void* stream);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,12 @@ SIGNATURES = {
     "ttts_rowdot_fwd": (I, [P, P, P, P, L, I, P]),
     "ttts_rowdot_bwd_workspace_bytes": (Z, [I]),
     "ttts_rowdot_bwd": (I, [P, P, P, P, P, P, P, Z, L, I, I, P, P]),
+    "ttts_decode_linear": (I, [P, L, L, P, P, P, L, P, L, L, P, L, L, I, I, I, I, I, P, P]),
+    "ttts_decode_frame_in": (I, [P, L, I, P, P, P, P, P, P, P, P, I, I, P, P]),
+    "ttts_decode_frame_out": (I, [P, P, P, P, P, P, L, P, L, I, I, I, P, P]),
+    "ttts_decode_layernorm": (I, [P, P, P, P, I, I, F, P, P]),
+    "ttts_decode_attention_workspace_bytes": (Z, [I, I, I, I]),
+    "ttts_decode_attention": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P]),
 }
 
 _lib = None
