@@ -58,13 +58,19 @@ typedef struct ttts_step_state {
  * threshold.  The caller resets it with one small host-to-device copy per call: t = 1, t_end = max_len (the buffers hold
  * t_end rows of frames), stop_frame = -1.  ttts_decode_frame_out records the first frame at which every row's stop
  * probability reaches the threshold in stop_frame, then advances t.  Every decode kernel returns at once when
- * t >= t_end or stop_frame >= 0. */
+ * t >= t_end or stop_frame >= 0.
+ * Per-row state (ABI v16): the ttts_decode_*_rows entry points also take `row_end`, B int64 on the device (allocated up to a
+ * multiple of 4 entries), reset to -1 by the
+ * same copy when it is laid out right behind the state: row_end[b] > 0 is the frame at which utterance b ended, anything else
+ * says it is still running.  With TTTS_DECODE_PER_ROW in `flags`, ttts_decode_frame_out_rows latches row_end[b] = t the first
+ * time row b reaches the threshold and sets stop_frame at the frame that leaves no row running. */
+#define TTTS_DECODE_PER_ROW 1
 typedef struct ttts_decode_state {
     int64_t t;            /*  0: the frame being decoded (1-based: frame t is written to ys[:, t], frame 0 is the go frame) */
     int64_t t_end;        /*  8: max_len */
     int64_t stop_frame;   /* 16: first all-stop frame, -1 until one occurs */
     float stop_threshold; /* 24: stop when sigmoid(stop logit) >= threshold for every row */
-    int32_t reserved;     /* 28 */
+    int32_t flags;        /* 28: TTTS_DECODE_PER_ROW or 0; read by ttts_decode_frame_out_rows only */
 } ttts_decode_state;
 
 const char* ttts_last_error(void);
@@ -555,6 +561,46 @@ size_t ttts_decode_attention_workspace_bytes(int B, int H, int head_dim, int max
 int ttts_decode_attention(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
                           const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
                           int max_keys, const ttts_decode_state* st, void* stream);
+
+/* ---- ABI v16: per-utterance ends and alignment rows (decode.hip) ------------------------------------------------------
+ * The same kernels with per-row state: `row_end` (B int64, device, required; see ttts_decode_state) names the rows that have
+ * ended.  An ended row is neither read nor written -- its activation rows, its K/V cache row, ys, stop and map rows keep what
+ * they held -- and its attention workgroups, combine and LayerNorm waves return before their first load; a row still running
+ * gets bit for bit what the entry point without `row_end` gives it.  Row m of every (M, ...) operand belongs to row_end[m].
+ * The GEMV and stop kernels read the end frames of four rows at once: `row_end` must be readable up to M rounded up to a
+ * multiple of 4 entries (the entries behind M are read, never acted on and never written).
+ * Everything else as ttts_decode_linear / _frame_in / _layernorm. */
+int ttts_decode_linear_rows(const float* x, int64_t ldx, int64_t x_tstride, const float* w, const float* bias,
+                            const float* residual, int64_t ldr, float* y, int64_t ldy, int64_t y_tstride, float* y2, int64_t ldy2,
+                            int64_t y2_tstride, int n_split, int M, int N, int K, int act, const int64_t* row_end,
+                            const ttts_decode_state* st, void* stream);
+int ttts_decode_frame_in_rows(const float* ys, int64_t ld_ys, int n_mels, const float* w1, const float* b1, const float* w2,
+                              const float* b2, const float* pe, const float* alpha, float* tmp, float* out, int B, int d,
+                              const int64_t* row_end, const ttts_decode_state* st, void* stream);
+int ttts_decode_layernorm_rows(const float* x, const float* gamma, const float* beta, float* y, int M, int d, float eps,
+                               const int64_t* row_end, const ttts_decode_state* st, void* stream);
+/* Frame out with per-row ends: heads and stop logits of the running rows as ttts_decode_frame_out.  st->flags without
+ * TTTS_DECODE_PER_ROW: the decision of ttts_decode_frame_out (every running row at or above the threshold at this frame), row_end
+ * is only read.  With it: a running row with 1 / (1 + expf(-stop)) >= st->stop_threshold gets row_end[b] = t (the first
+ * crossing: the row is skipped afterwards), and st->stop_frame = t once no row is left running; st->t = t + 1 either way. */
+int ttts_decode_frame_out_rows(const float* x, const float* w_mel, const float* b_mel, const float* w_stop, const float* b_stop,
+                               float* ys, int64_t ld_ys, float* stop, int64_t ld_stop, int B, int d, int n_mels, int64_t* row_end,
+                               ttts_decode_state* st, void* stream);
+/* ttts_decode_attention with per-row ends and, map != NULL, the attention weights of this frame (the cross-attention maps the
+ * training forward returns as `alignments`, model/layers.py:54-74 need_weights=True, average_attn_weights=False): row t - 1 of
+ * plane (b, h) at map + (b * H + h) * map_ld_head + (t - 1) * map_ld_row receives softmax(q k^T / sqrt(head_dim)) over the keys
+ * below len and zeros from there to max_keys.  The key blocks write their unnormalised weights and the combine launch rescales
+ * them, block by block, with the factors it applies to the context vector.  map_rows: frames a plane holds (nothing is written
+ * when t - 1 >= map_rows); map_ld_row >= max_keys, map_ld_head >= map_rows * map_ld_row.  map == NULL: no map code runs. */
+int ttts_decode_attention_rows(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
+                               const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
+                               int max_keys, const int64_t* row_end, float* map, int64_t map_ld_head, int64_t map_ld_row,
+                               int map_rows, const ttts_decode_state* st, void* stream);
+/* x (outer, T, C) contiguous: rows t >= lens[o / group] of slice o := 0 (lens int64 on the device, clamped to [0, T]; group
+ * slices share one length: the heads of an attention map).  The frames behind each utterance's end in the outputs of a batched
+ * synthesis, and in the post-net's input and every layer's output (a convolution over a zero-padded batch does not keep them
+ * zero by itself).  16-byte stores when C % 4 == 0 and x is 16-byte aligned.  outer <= 65535. */
+int ttts_mask_rows(float* x, const int64_t* lens, int64_t outer, int group, int64_t T, int64_t C, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,20 @@
 Every call decodes max_len - 1 = 1499 frames (stop_threshold 2.0: a sigmoid never reaches it) of Tp = 100 phonemes.  Per
 configuration: one warm-up call of each path, then the median wall time (host clock around the call, which ends in a
 device-to-host read) over `reps` calls.  Prints one JSON line per configuration and, with --out, writes them as a list.
+
+    python tools/synthesis_bench.py --ragged [--configs base:16,base:64] [--reps 5] [--maps-at 16] [--out FILE]
+                                             [--save-head FILE | --load-head FILE --one-call]
+
+Batched synthesis with per-utterance ends (`Synthesizer.synthesize`).  The stop head is refitted by least squares (it is a
+combination of the mel head's rows, so the frames stay what they were) towards one ramp per row whose zero crossings are spread
+evenly over frames 300 .. 1499; an exact fit is not available at B x 1499 equations, so the row ends are then read from the
+engine's own free-running stop probabilities at threshold 0.5 (probe, then threshold) and reported as they came out.  Per
+configuration, alternating the calls within every repetition: `__call__` at threshold 2.0 (what a caller had to run before:
+B x 1499 frames), `synthesize` at threshold 2.0 (no row ends early: the cost of the per-row state), `synthesize` at 0.5 (spread
+ends), and at B = --maps-at the same with alignment maps.  Reports the frames produced (mel_lens.sum()), the live-row fraction
+mel_lens.sum() / (B x 1499) -- the bound a call that skipped all finished work at no cost would reach -- and the achieved
+time ratio.  --save-head / --load-head --one-call: fit once, then run exactly one `synthesize` call in a process of its own
+(for a kernel trace of one call).
 """
 from __future__ import annotations
 
@@ -67,19 +81,121 @@ def run(cfg_name: str, B: int, reps: int, skip_inference: bool) -> dict:
     return rec
 
 
+def _fit_ragged_stop_head(m, mel, lo=300, hi=MAX_LEN - 1, slope=0.01):
+    """least squares: stop logit of frame f (1-based) of row b -> slope * (f - c_b), c_b spread evenly over lo .. hi"""
+    B, F = mel.shape[:2]
+    wm, bm = m.linear1.linear.weight.detach().double().cpu(), m.linear1.linear.bias.detach().double().cpu()
+    A = (mel.double().cpu() - bm).reshape(-1, wm.shape[0])
+    c = torch.linspace(lo, hi, B, dtype=torch.float64)
+    f = torch.arange(1, F + 1, dtype=torch.float64)
+    y = (slope * (f.view(1, F) - c.view(B, 1))).clamp(-4.0, 4.0).reshape(-1)
+    a = torch.linalg.lstsq(A, y.unsqueeze(1)).solution[:, 0]
+    m.linear2.linear.weight.data.copy_((a @ wm).float().view(1, -1))
+    m.linear2.linear.bias.data.zero_()
+    return [int(round(x)) for x in c.tolist()]
+
+
+def _alternating(fns: dict, reps: int) -> dict:
+    """{name: [seconds]}: one warm-up of each, then `reps` rounds calling every fn once, in turn"""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    return times
+
+
+def run_ragged(cfg_name: str, B: int, reps: int, maps: bool, save_head, load_head, one_call: bool) -> dict:
+    torch.manual_seed(0)
+    cfg = model_config(cfg_name)
+    m = TransformerTTS(**cfg, device="cuda").to("cuda").eval()
+    batch = synth_batch(B, TP, 870, cfg["n_mels"], cfg["n_phon"], ragged=False, seed=7)
+    ph, pl = batch["phoneme"].cuda(), batch["phoneme_lens"].cuda()
+    frames = MAX_LEN - 1
+    synth = Synthesizer(m)
+    if load_head:
+        head = torch.load(load_head)
+        m.linear2.linear.weight.data.copy_(head["weight"])
+        m.linear2.linear.bias.data.copy_(head["bias"])
+        if one_call:
+            out = synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5, alignments=maps)
+            torch.cuda.synchronize()
+            return {"config": cfg_name, "B": B, "one_call": True, "alignments": maps,
+                    "frames_produced": int(out["mel_lens"].sum()), "frames_decoded": int(out["mel_lens"].max())}
+        targets = None
+    else:
+        probe = synth(ph, pl, max_len=MAX_LEN, stop_threshold=STOP)
+        targets = _fit_ragged_stop_head(m, probe["pred_melspec"])
+    if save_head:
+        torch.save({"weight": m.linear2.linear.weight.detach().cpu(), "bias": m.linear2.linear.bias.detach().cpu()}, save_head)
+    free = synth(ph, pl, max_len=MAX_LEN, stop_threshold=STOP)
+    p = torch.sigmoid(free["pred_stop"][..., 0].double()).cpu()
+    hit = p >= 0.5
+    want = torch.where(hit.any(dim=1), hit.double().argmax(dim=1) + 1, torch.full((B,), frames))
+    out = synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5)
+    lens = out["mel_lens"].cpu()
+    assert lens.tolist() == want.tolist(), (lens.tolist(), want.tolist())     # (a decision within fp32 noise of 0.5 would show here)
+    for b, n in enumerate(lens.tolist()):
+        assert torch.equal(out["pred_melspec"][b, :n], free["pred_melspec"][b, :n]), b
+        assert bool((out["pred_melspec"][b, n:] == 0).all()) and bool((out["post_melspec"][b, n:] == 0).all()), b
+    fns = {"call_full": lambda: synth(ph, pl, max_len=MAX_LEN, stop_threshold=STOP),
+           "synthesize_full": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=STOP),
+           "synthesize_ragged": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5)}
+    if maps:
+        fns["synthesize_ragged_maps"] = lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5, alignments=True)
+        fns["synthesize_full_maps"] = lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=STOP, alignments=True)
+    times = _alternating(fns, reps)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    produced = int(lens.sum())
+    rec = {"config": cfg_name, "B": B, "Tp": TP, "max_len": MAX_LEN, "reps": reps, "chunk": synth.chunk,
+           "target_ends": targets, "mel_lens": sorted(lens.tolist()), "frames_decoded": int(lens.max()),
+           "frames_produced": produced, "frames_parent_semantics": B * frames,
+           "live_row_fraction": round(produced / (B * frames), 4),
+           "min_margin_from_threshold": float((p - 0.5).abs().min()),
+           "captures": synth.captures, "static_bytes_per_shape": sum(synth.shape_bytes().values())}
+    for k, v in times.items():
+        rec[k + "_ms"] = round(med[k] * 1e3, 2)
+        rec[k + "_ms_all"] = [round(x * 1e3, 2) for x in v]
+    rec["synthesize_full_over_call_full"] = round(med["synthesize_full"] / med["call_full"], 4)
+    rec["synthesize_ragged_over_call_full"] = round(med["synthesize_ragged"] / med["call_full"], 4)
+    rec["synthesize_ragged_us_per_produced_frame"] = round(med["synthesize_ragged"] * 1e6 / produced, 2)
+    rec["call_full_us_per_produced_frame"] = round(med["call_full"] * 1e6 / (B * frames), 2)
+    if maps:
+        rec["maps_on_over_off_ragged"] = round(med["synthesize_ragged_maps"] / med["synthesize_ragged"], 4)
+        rec["maps_on_over_off_full"] = round(med["synthesize_full_maps"] / med["synthesize_full"], 4)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="base:1,base:16,base:64,scaled:1")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-inference", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ragged", action="store_true", help="batched synthesis with per-utterance ends (see the module docstring)")
+    ap.add_argument("--maps-at", type=int, default=16, help="--ragged: the batch size that is also timed with alignment maps")
+    ap.add_argument("--save-head", default=None, help="--ragged: save the fitted stop head")
+    ap.add_argument("--load-head", default=None, help="--ragged: use a saved stop head instead of probing and fitting")
+    ap.add_argument("--one-call", action="store_true", help="--ragged --load-head: exactly one synthesize call, no timing")
     a = ap.parse_args()
+    if a.one_call and not (a.ragged and a.load_head):
+        raise SystemExit("synthesis_bench: --one-call needs --ragged and --load-head")
     if not torch.cuda.is_available():
         raise SystemExit("synthesis_bench: needs the HIP device")
+    if a.ragged and a.configs == ap.get_default("configs"):
+        a.configs = "base:16,base:64"
     recs = []
     for item in a.configs.split(","):
         name, B = item.split(":")
-        rec = run(name, int(B), a.reps, a.skip_inference)
+        if a.ragged:
+            rec = run_ragged(name, int(B), a.reps, int(B) == a.maps_at, a.save_head, a.load_head, a.one_call)
+        else:
+            rec = run(name, int(B), a.reps, a.skip_inference)
         print(json.dumps(rec), flush=True)
         recs.append(rec)
     if a.out:

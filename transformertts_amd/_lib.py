@@ -118,6 +118,12 @@ SIGNATURES = {
     "ttts_decode_layernorm": (I, [P, P, P, P, I, I, F, P, P]),
     "ttts_decode_attention_workspace_bytes": (Z, [I, I, I, I]),
     "ttts_decode_attention": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P]),
+    "ttts_decode_linear_rows": (I, [P, L, L, P, P, P, L, P, L, L, P, L, L, I, I, I, I, I, P, P, P]),
+    "ttts_decode_frame_in_rows": (I, [P, L, I, P, P, P, P, P, P, P, P, I, I, P, P, P]),
+    "ttts_decode_frame_out_rows": (I, [P, P, P, P, P, P, L, P, L, I, I, I, P, P, P]),
+    "ttts_decode_layernorm_rows": (I, [P, P, P, P, I, I, F, P, P, P]),
+    "ttts_decode_attention_rows": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P, L, L, I, P, P]),
+    "ttts_mask_rows": (I, [P, P, L, I, L, L, P]),
 }
 
 _lib = None

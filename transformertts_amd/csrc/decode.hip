@@ -6,6 +6,9 @@
 // every frame and every call; every kernel returns at once when t >= t_end or a stop frame has been recorded.
 // Summation orders are fixed (per lane in index order, then the wave butterfly, then waves / key blocks in index order) and
 // depend on neither M, B nor the buffer capacities: a synthesized call is bitwise reproducible.  No atomics.
+// The *_rows entry points add per-row state: row_end[b] > 0 says utterance b ended at that frame, and every per-row unit of
+// work (an attention workgroup, a combine or LayerNorm wave, a GEMV row's loads and stores) returns before its first global
+// load of that row; the rows still running compute exactly what they compute with no row ended.
 #include "ttts_common.h"
 
 namespace ttts {
@@ -18,7 +21,17 @@ constexpr int LN_PER = 16;        // decode LayerNorm: d <= 64 * LN_PER
 
 __device__ __forceinline__ bool decode_done(const ttts_decode_state* st, int64_t& t) {
     t = st->t;
-    return t >= st->t_end || st->stop_frame >= 0;
+    const int64_t t_end = st->t_end, stop_frame = st->stop_frame;      // one scalar read of the block, not two dependent ones
+    return (t >= t_end) | (stop_frame >= 0);
+}
+
+// row_end == NULL (the entry points without per-row state): no row ever ends.  The load is unconditional (a field of the state
+// stands in for a missing array) and every kernel issues it together with the state read, before the branch on either: the
+// per-row state then costs no memory round trip of its own.
+__device__ __forceinline__ bool row_ended(const int64_t* row_end, const ttts_decode_state* st, int m) {
+    const int64_t* p = row_end != nullptr ? row_end + m : &st->stop_frame;
+    const int64_t v = *p;
+    return (row_end != nullptr) & (v > 0);
 }
 
 __device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
@@ -43,10 +56,12 @@ struct DecLinArgs {
     long ldy2, y2_ts;
     int n_split, M, N, K, act;
     const ttts_decode_state* st;
+    const int64_t* row_end;  // NULL, or (M rounded up to a multiple of 4): rows with row_end[m] > 0 are neither read nor written
 };
 
 // y[M,N] = act(x . w^T + b) (+ res) (+ alpha pe[t-1]).  Wave = NC output columns; lane l holds the float4 chunks l, l+64, ...
 // of each column's weight row (KC of them); one workgroup = 4 waves x DEC_ROWS rows, its activation rows loaded up front.
+// Ended rows (row_end) cost the workgroup nothing but the weight stream it shares with its other rows.
 template <int KC, int NC>
 __global__ __launch_bounds__(256) void decode_linear_kernel(const DecLinArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -63,11 +78,24 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const DecLinArgs a) 
             w[c][j] = k4 < K4 ? wr[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
+    const int m0 = blockIdx.y * DEC_ROWS;
+    // the four rows' end frames in ONE scalar read issued with the state read (row_end is readable up to a multiple of four
+    // entries; without it the 32-byte state block stands in and is ignored)
+    const bool has_rows = a.row_end != nullptr;
+    const int64_t* rp = has_rows ? a.row_end + m0 : reinterpret_cast<const int64_t*>(a.st);
+    const int64_t re[DEC_ROWS] = {rp[0], rp[1], rp[2], rp[3]};
     int64_t t;
-    if (decode_done(a.st, t)) return;
+    const bool done = decode_done(a.st, t);
+    bool ended[DEC_ROWS];
+    bool all_ended = true;
+#pragma unroll
+    for (int r = 0; r < DEC_ROWS; ++r) {
+        ended[r] = has_rows & (re[r] > 0);
+        all_ended = all_ended & (ended[r] | (m0 + r >= a.M));
+    }
+    if (done | all_ended) return;             // (uniform over the workgroup)
     const long tr = (long)(t - 1);
     // the workgroup's rows: every activation load is issued before the first product (one L2 round trip, not one per row)
-    const int m0 = blockIdx.y * DEC_ROWS;
     float4 xv[DEC_ROWS][KC];
 #pragma unroll
     for (int r = 0; r < DEC_ROWS; ++r) {
@@ -76,14 +104,14 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const DecLinArgs a) 
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
             const int k4 = lane + 64 * j;
-            xv[r][j] = k4 < K4 ? xr[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[r][j] = (k4 < K4 && !ended[r]) ? xr[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
 #pragma unroll
     for (int r = 0; r < DEC_ROWS; ++r) {
         const int m = m0 + r;
         if (m >= a.M) break;
-        float acc[NC];
+        float acc[NC];                        // (an ended row's products run on zeros: cheaper than a branch around them)
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             float s = 0.f;
@@ -94,7 +122,7 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const DecLinArgs a) 
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int n = n0 + c;
-            if (lane != c || n >= a.N) continue;
+            if (lane != c || n >= a.N || ended[r]) continue;
             float v = acc[c];
             if (a.bias != nullptr) v += a.bias[n];
             if (a.act == TTTS_ACT_RELU) v = fmaxf(v, 0.f);
@@ -151,10 +179,13 @@ int check_decode_linear(const DecLinArgs& a, const char* what) {
 // One workgroup: wave w takes rows 4w .. 4w+3, 4w+16 .. 4w+19, ...; stop[m, t-1] = x[m] . w + b; then the frame is an
 // all-stop frame when every row has 1 / (1 + expf(-stop)) >= threshold (torch.sigmoid(stop) >= thr away from exact ties);
 // thread 0 records it and advances t.
+// With row_end: ended rows are neither read nor written.  Under TTTS_DECODE_PER_ROW (st->flags) a row that reaches the
+// threshold has row_end[m] = t latched (its first crossing: it is skipped from then on), and the frame that leaves no row
+// running is the stop frame; without the flag the decision is the all-rows-at-this-frame one above, over the running rows.
 template <int KC>
 __global__ __launch_bounds__(256) void decode_stop_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ b, float* __restrict__ stop, long ld_stop,
-                                                          int M, int K, ttts_decode_state* st) {
+                                                          int M, int K, int64_t* row_end, ttts_decode_state* st) {
     __shared__ int all_rows[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K4 = K >> 2;
@@ -165,12 +196,20 @@ __global__ __launch_bounds__(256) void decode_stop_kernel(const float* __restric
         const int k4 = lane + 64 * j;
         wv[j] = k4 < K4 ? w4[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    // the wave's first four rows: one scalar read issued with the state read, as in decode_linear_kernel
+    const bool has_rows = row_end != nullptr;
+    const int64_t* rp = (has_rows && wave * 4 < M) ? row_end + wave * 4 : reinterpret_cast<const int64_t*>(st);
+    const int64_t first[4] = {rp[0], rp[1], rp[2], rp[3]};
     int64_t t;
     if (decode_done(st, t)) return;           // (uniform over the workgroup)
     const float thr = st->stop_threshold;
+    const bool per_row = row_end != nullptr && (st->flags & TTTS_DECODE_PER_ROW) != 0;
     const float bias = b != nullptr ? b[0] : 0.f;
     int ok = 1;
     for (int mb = wave * 4; mb < M; mb += 16) {            // four rows per wave at a time, their loads issued together
+        bool ended[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ended[r] = has_rows & (((mb == wave * 4 || !has_rows) ? first[r] : row_end[mb + r]) > 0);
         float4 xv[4][KC];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -178,20 +217,23 @@ __global__ __launch_bounds__(256) void decode_stop_kernel(const float* __restric
 #pragma unroll
             for (int j = 0; j < KC; ++j) {
                 const int k4 = lane + 64 * j;
-                xv[r][j] = k4 < K4 ? xr[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                xv[r][j] = (k4 < K4 && !ended[r]) ? xr[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int m = mb + r;
             if (m >= M) break;
+            if (ended[r]) continue;
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < KC; ++j) s = dot4(xv[r][j], wv[j], s);
             const float v = wave_sum(s) + bias;
             if (lane == 0) stop[(long)m * ld_stop + (t - 1)] = v;
             const float p = 1.0f / (1.0f + expf(-v));
-            ok &= (p >= thr) ? 1 : 0;
+            const bool cross = p >= thr;
+            if (per_row && cross && lane == 0) row_end[m] = t;
+            ok &= cross ? 1 : 0;
         }
     }
     if (lane == 0) all_rows[wave] = ok;
@@ -206,12 +248,14 @@ __global__ __launch_bounds__(256) void decode_stop_kernel(const float* __restric
 // ---------------------------------------------------------------- LayerNorm of the decoder rows
 __global__ __launch_bounds__(256) void decode_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ y, int M, int d,
-                                                               float eps, const ttts_decode_state* st) {
+                                                               float eps, const int64_t* __restrict__ row_end,
+                                                               const ttts_decode_state* st) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
     if (row >= M) return;
+    const bool ended = row_ended(row_end, st, row);
     int64_t t;
-    if (decode_done(st, t)) return;
+    if (decode_done(st, t) | ended) return;   // (uniform over the wave)
     const float* xr = x + (long)row * d;
     float v[LN_PER];
     float s = 0.f;
@@ -239,19 +283,30 @@ __global__ __launch_bounds__(256) void decode_layernorm_kernel(const float* __re
 // Workgroup (s, h, b) takes keys [64 s, 64 s + 64): wave w keys 16 w .. 16 w + 15, four lanes per key, each lane a contiguous
 // quarter of the head (HD / 16 float4).  Keys at or past the length are never loaded.  Partial (o[HD], max, sum) per block
 // goes to the workspace; the combine kernel adds the blocks below the length in block order.
-template <int HD>
+// MAPS: the unnormalised weight exp(s - m_block) of every key below the length also goes to row t - 1 of the (b, h) plane of
+// the attention map; the combine rescales that row with the factors it forms for the context vector.
+struct AttnMap {
+    float* p;                // (B, H, rows, ld_row) floats: plane (b, h) at p + (b * H + h) * ld_head, NULL without MAPS
+    long ld_head, ld_row;
+    int rows;                // frames the planes hold: row t - 1 is written when t - 1 < rows
+};
+
+template <int HD, bool MAPS>
 __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
                                                                   const float* __restrict__ v, long ld_row, long ld_batch,
                                                                   const int64_t* __restrict__ lens, float* __restrict__ ws, int H,
-                                                                  int nsplit, int max_keys, float scale, const ttts_decode_state* st) {
+                                                                  int nsplit, int max_keys, float scale,
+                                                                  const int64_t* __restrict__ row_end, const AttnMap map,
+                                                                  const ttts_decode_state* st) {
     constexpr int CH = HD / 16;               // float4 per lane
     constexpr int WS = HD + 4;                // workspace floats per block
     __shared__ float red_m[4], red_l[4];
     __shared__ float4 red_o[4][HD / 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const bool ended = row_ended(row_end, st, b);
     int64_t t;
-    if (decode_done(st, t)) return;
+    if (decode_done(st, t) | ended) return;   // (uniform over the workgroup)
     long len = lens != nullptr ? (long)lens[b] : (long)t;
     len = len < (long)max_keys ? len : (long)max_keys;
     const int key0 = s * ATTN_KEYS;
@@ -282,6 +337,10 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const float* _
     __syncthreads();
     const float mb = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));   // finite: key0 < len
     const float p = live ? expf(sc - mb) : 0.f;
+    if (MAPS) {
+        if (live && sub == 0 && t - 1 < (int64_t)map.rows)
+            map.p[((long)b * H + h) * map.ld_head + (long)(t - 1) * map.ld_row + key] = p;
+    }
     const float wl = wave_sum(sub == 0 ? p : 0.f);
     float4 o[CH];
 #pragma unroll
@@ -319,14 +378,17 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const float* _
 }
 
 // one wave per (head, utterance): out = sum_s o_s e^(m_s - m) / sum_s l_s e^(m_s - m) over the blocks below the length
-template <int HD>
+// MAPS: map row t - 1, key j of block s = (its unnormalised weight * e^(m_s - m)) / l below the length, 0 from there to max_keys
+template <int HD, bool MAPS>
 __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __restrict__ ws, const int64_t* __restrict__ lens,
                                                                  float* __restrict__ out, long ldo, int H, int nsplit, int max_keys,
+                                                                 const int64_t* __restrict__ row_end, const AttnMap map,
                                                                  const ttts_decode_state* st) {
     constexpr int WS = HD + 4;
     const int lane = threadIdx.x, h = blockIdx.x, b = blockIdx.y;
+    const bool ended = row_ended(row_end, st, b);
     int64_t t;
-    if (decode_done(st, t)) return;
+    if (decode_done(st, t) | ended) return;   // (uniform over the wave)
     long len = lens != nullptr ? (long)lens[b] : (long)t;
     len = len < (long)max_keys ? len : (long)max_keys;
     const int nblk = len > 0 ? (int)((len + ATTN_KEYS - 1) / ATTN_KEYS) : 0;
@@ -344,19 +406,102 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
     float* orow = out + (long)b * ldo + (long)h * HD;
     if (lane < HD) orow[lane] = o0 * inv;
     if (lane + 64 < HD) orow[lane + 64] = o1 * inv;
+    if (MAPS) {
+        if (t - 1 >= (int64_t)map.rows) return;
+        float* mrow = map.p + ((long)b * H + h) * map.ld_head + (long)(t - 1) * map.ld_row;
+        for (int s = 0; s < nsplit; ++s) {
+            const int key = s * ATTN_KEYS + lane;
+            if (key >= max_keys) break;
+            float a = 0.f;
+            if (s < nblk && key < len) a = (mrow[key] * expf(p[s * WS + HD] - m)) * inv;
+            mrow[key] = a;
+        }
+    }
 }
 
 int attn_nsplit(int max_keys) { return cdiv(max_keys, ATTN_KEYS); }
 
-template <int HD>
-void launch_decode_attention_t(const float* q, long ldq, const float* k, const float* v, long ld_row, long ld_batch,
-                               const int64_t* lens, float* out, long ldo, float* ws, int B, int H, int max_keys,
-                               const ttts_decode_state* st, hipStream_t stream) {
-    const int ns = attn_nsplit(max_keys);
+struct AttnArgs {
+    const float *q, *k, *v;
+    long ldq, ld_row, ld_batch;
+    const int64_t* lens;
+    float* out;
+    long ldo;
+    float* ws;
+    int B, H, max_keys;
+    const int64_t* row_end;
+    AttnMap map;
+    const ttts_decode_state* st;
+};
+
+template <int HD, bool MAPS>
+void launch_decode_attention_tm(const AttnArgs& a, hipStream_t stream) {
+    const int ns = attn_nsplit(a.max_keys);
     const float scale = 1.0f / sqrtf((float)HD);
-    hipLaunchKernelGGL((decode_attn_partial_kernel<HD>), dim3(ns, H, B), dim3(256), 0, stream, q, ldq, k, v, ld_row, ld_batch,
-                       lens, ws, H, ns, max_keys, scale, st);
-    hipLaunchKernelGGL((decode_attn_combine_kernel<HD>), dim3(H, B), dim3(64), 0, stream, ws, lens, out, ldo, H, ns, max_keys, st);
+    hipLaunchKernelGGL((decode_attn_partial_kernel<HD, MAPS>), dim3(ns, a.H, a.B), dim3(256), 0, stream, a.q, a.ldq, a.k, a.v,
+                       a.ld_row, a.ld_batch, a.lens, a.ws, a.H, ns, a.max_keys, scale, a.row_end, a.map, a.st);
+    hipLaunchKernelGGL((decode_attn_combine_kernel<HD, MAPS>), dim3(a.H, a.B), dim3(64), 0, stream, a.ws, a.lens, a.out, a.ldo,
+                       a.H, ns, a.max_keys, a.row_end, a.map, a.st);
+}
+
+template <int HD>
+void launch_decode_attention_t(const AttnArgs& a, hipStream_t stream) {
+    if (a.map.p != nullptr) launch_decode_attention_tm<HD, true>(a, stream);
+    else launch_decode_attention_tm<HD, false>(a, stream);
+}
+
+int check_decode_attention(const AttnArgs& a, int head_dim, size_t ws_bytes, const char* what) {
+    TTTS_REQUIRE(a.q && a.k && a.v && a.out && a.ws && a.st, "%s: null pointer", what);
+    TTTS_REQUIRE(a.B >= 1 && a.H >= 1 && a.B <= 65535 && a.H <= 65535 && a.max_keys >= 1, "%s: bad sizes B=%d H=%d max_keys=%d",
+                 what, a.B, a.H, a.max_keys);
+    TTTS_REQUIRE(head_dim >= 16 && head_dim <= 128 && head_dim % 16 == 0, "%s: head_dim=%d (a multiple of 16 up to 128)", what,
+                 head_dim);
+    TTTS_REQUIRE(a.ldq % 4 == 0 && a.ld_row % 4 == 0 && a.ld_batch % 4 == 0 && a.ldq >= (long)a.H * head_dim &&
+                 a.ld_row >= (long)a.H * head_dim && a.ld_batch >= 0 && a.ldo >= (long)a.H * head_dim,
+                 "%s: strides ldq=%ld ld_row=%ld ld_batch=%ld ldo=%ld (multiples of 4, >= H * head_dim)", what, a.ldq, a.ld_row,
+                 a.ld_batch, a.ldo);
+    TTTS_REQUIRE((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.ws) & 15) == 0,
+                 "%s: q, k, v and ws must be 16-byte aligned", what);
+    TTTS_REQUIRE(ws_bytes >= ttts_decode_attention_workspace_bytes(a.B, a.H, head_dim, a.max_keys),
+                 "%s: workspace of %zu bytes < %zu", what, ws_bytes,
+                 ttts_decode_attention_workspace_bytes(a.B, a.H, head_dim, a.max_keys));
+    return TTTS_OK;
+}
+
+int launch_decode_attention(const AttnArgs& a, int head_dim, hipStream_t s, const char* what) {
+    switch (head_dim) {
+        case 16: launch_decode_attention_t<16>(a, s); break;
+        case 32: launch_decode_attention_t<32>(a, s); break;
+        case 48: launch_decode_attention_t<48>(a, s); break;
+        case 64: launch_decode_attention_t<64>(a, s); break;
+        case 80: launch_decode_attention_t<80>(a, s); break;
+        case 96: launch_decode_attention_t<96>(a, s); break;
+        case 112: launch_decode_attention_t<112>(a, s); break;
+        default: launch_decode_attention_t<128>(a, s); break;
+    }
+    TTTS_LAUNCH_CHECK(what);
+    return TTTS_OK;
+}
+
+// ---------------------------------------------------------------- rows at or past a length := 0
+// x is (outer, T, C); slice o keeps rows < lens[o / group].  Workgroup (c, o) strides over the tail of slice o, 16-byte
+// stores when C and the slice offset allow it (VEC), single floats otherwise.
+template <bool VEC>
+__global__ __launch_bounds__(256) void mask_rows_kernel(float* __restrict__ x, const int64_t* __restrict__ lens, int group, long T,
+                                                        long C) {
+    const long o = blockIdx.y;
+    long len = (long)lens[o / group];
+    len = len < 0 ? 0 : (len > T ? T : len);
+    float* base = x + o * T * C;
+    const long first = len * C, total = T * C;
+    const long step = (long)gridDim.x * blockDim.x;
+    if (VEC) {
+        float4* b4 = reinterpret_cast<float4*>(base);
+        for (long i = (first >> 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < (total >> 2); i += step)
+            b4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        for (long i = first + (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) base[i] = 0.f;
+    }
 }
 
 }  // namespace
@@ -366,68 +511,138 @@ using namespace ttts;
 
 extern "C" {
 
-int ttts_decode_linear(const float* x, int64_t ldx, int64_t x_tstride, const float* w, const float* bias, const float* residual,
-                       int64_t ldr, float* y, int64_t ldy, int64_t y_tstride, float* y2, int64_t ldy2, int64_t y2_tstride,
-                       int n_split, int M, int N, int K, int act, const ttts_decode_state* st, void* stream) {
+// the stop kernel of the frame-out entry points
+static int launch_decode_stop(const float* x, const float* w_stop, const float* b_stop, float* stop, long ld_stop, int B, int d,
+                              int64_t* row_end, ttts_decode_state* st, hipStream_t s) {
+    const int kc = cdiv(d, 256);
+    if (kc <= 1) hipLaunchKernelGGL(decode_stop_kernel<1>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, ld_stop, B, d, row_end, st);
+    else if (kc <= 2) hipLaunchKernelGGL(decode_stop_kernel<2>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, ld_stop, B, d, row_end, st);
+    else if (kc <= 4) hipLaunchKernelGGL(decode_stop_kernel<4>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, ld_stop, B, d, row_end, st);
+    else if (kc <= 8) hipLaunchKernelGGL(decode_stop_kernel<8>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, ld_stop, B, d, row_end, st);
+    else hipLaunchKernelGGL(decode_stop_kernel<16>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, ld_stop, B, d, row_end, st);
+    return TTTS_OK;
+}
+
+static int decode_linear_impl(const char* what, const float* x, int64_t ldx, int64_t x_tstride, const float* w, const float* bias,
+                              const float* residual, int64_t ldr, float* y, int64_t ldy, int64_t y_tstride, float* y2, int64_t ldy2,
+                              int64_t y2_tstride, int n_split, int M, int N, int K, int act, const int64_t* row_end,
+                              const ttts_decode_state* st, void* stream) {
     DecLinArgs a{x, (long)ldx, (long)x_tstride, w, bias, residual, (long)ldr, nullptr, nullptr, y, (long)ldy, (long)y_tstride,
-                 y2, (long)ldy2, (long)y2_tstride, n_split, M, N, K, act, st};
-    TTTS_REQUIRE(residual == nullptr || ldr >= N || M == 1, "decode_linear: ldr=%ld < N=%d", (long)ldr, N);
-    const int rc = check_decode_linear(a, "decode_linear");
+                 y2, (long)ldy2, (long)y2_tstride, n_split, M, N, K, act, st, row_end};
+    TTTS_REQUIRE(residual == nullptr || ldr >= N || M == 1, "%s: ldr=%ld < N=%d", what, (long)ldr, N);
+    const int rc = check_decode_linear(a, what);
     if (rc != TTTS_OK) return rc;
     return launch_decode_linear(a, (hipStream_t)stream);
 }
 
-int ttts_decode_frame_in(const float* ys, int64_t ld_ys, int n_mels, const float* w1, const float* b1, const float* w2,
-                         const float* b2, const float* pe, const float* alpha, float* tmp, float* out, int B, int d,
-                         const ttts_decode_state* st, void* stream) {
-    TTTS_REQUIRE(ys && w1 && w2 && pe && alpha && tmp && out && st, "decode_frame_in: null pointer");
+static int decode_frame_in_impl(const char* what, const float* ys, int64_t ld_ys, int n_mels, const float* w1, const float* b1,
+                                const float* w2, const float* b2, const float* pe, const float* alpha, float* tmp, float* out, int B,
+                                int d, const int64_t* row_end, const ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(ys && w1 && w2 && pe && alpha && tmp && out && st, "%s: null pointer", what);
     TTTS_REQUIRE(B >= 1 && d >= 4 && d % 4 == 0 && n_mels >= 4 && n_mels % 4 == 0 && ld_ys >= n_mels,
-                 "decode_frame_in: bad sizes B=%d d=%d n_mels=%d ld_ys=%ld (d, n_mels multiples of 4)", B, d, n_mels, (long)ld_ys);
-    TTTS_REQUIRE(((uintptr_t)tmp & 15) == 0, "decode_frame_in: tmp must be 16-byte aligned");
+                 "%s: bad sizes B=%d d=%d n_mels=%d ld_ys=%ld (d, n_mels multiples of 4)", what, B, d, n_mels, (long)ld_ys);
+    TTTS_REQUIRE(((uintptr_t)tmp & 15) == 0, "%s: tmp must be 16-byte aligned", what);
     DecLinArgs l1{ys, (long)ld_ys, (long)n_mels, w1, b1, nullptr, 0, nullptr, nullptr, tmp, (long)d, 0, nullptr, 0, 0, d, B, d,
-                  n_mels, TTTS_ACT_RELU, st};
-    DecLinArgs l2{tmp, (long)d, 0, w2, b2, nullptr, 0, pe, alpha, out, (long)d, 0, nullptr, 0, 0, d, B, d, d, TTTS_ACT_RELU, st};
-    int rc = check_decode_linear(l1, "decode_frame_in (pre-net linear1)");
-    if (rc == TTTS_OK) rc = check_decode_linear(l2, "decode_frame_in (pre-net linear2)");
+                  n_mels, TTTS_ACT_RELU, st, row_end};
+    DecLinArgs l2{tmp, (long)d, 0, w2, b2, nullptr, 0, pe, alpha, out, (long)d, 0, nullptr, 0, 0, d, B, d, d, TTTS_ACT_RELU, st,
+                  row_end};
+    char name[96];
+    snprintf(name, sizeof name, "%s (pre-net linear1)", what);
+    int rc = check_decode_linear(l1, name);
+    snprintf(name, sizeof name, "%s (pre-net linear2)", what);
+    if (rc == TTTS_OK) rc = check_decode_linear(l2, name);
     if (rc != TTTS_OK) return rc;
     rc = launch_decode_linear(l1, (hipStream_t)stream);
     if (rc != TTTS_OK) return rc;
     return launch_decode_linear(l2, (hipStream_t)stream);
 }
 
-int ttts_decode_frame_out(const float* x, const float* w_mel, const float* b_mel, const float* w_stop, const float* b_stop,
-                          float* ys, int64_t ld_ys, float* stop, int64_t ld_stop, int B, int d, int n_mels,
-                          ttts_decode_state* st, void* stream) {
-    TTTS_REQUIRE(x && w_mel && w_stop && ys && stop && st, "decode_frame_out: null pointer");
+static int decode_frame_out_impl(const char* what, const float* x, const float* w_mel, const float* b_mel, const float* w_stop,
+                                 const float* b_stop, float* ys, int64_t ld_ys, float* stop, int64_t ld_stop, int B, int d,
+                                 int n_mels, int64_t* row_end, ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(x && w_mel && w_stop && ys && stop && st, "%s: null pointer", what);
     TTTS_REQUIRE(B >= 1 && d >= 4 && d % 4 == 0 && d <= DEC_KMAX && n_mels >= 1 && ld_ys >= n_mels && ld_stop >= 1,
-                 "decode_frame_out: bad sizes B=%d d=%d n_mels=%d ld_ys=%ld ld_stop=%ld", B, d, n_mels, (long)ld_ys, (long)ld_stop);
-    TTTS_REQUIRE(((uintptr_t)w_stop & 15) == 0, "decode_frame_out: w_stop must be 16-byte aligned");
+                 "%s: bad sizes B=%d d=%d n_mels=%d ld_ys=%ld ld_stop=%ld", what, B, d, n_mels, (long)ld_ys, (long)ld_stop);
+    TTTS_REQUIRE(((uintptr_t)w_stop & 15) == 0, "%s: w_stop must be 16-byte aligned", what);
     // frame t of ys: row (t - 1) + 1
     DecLinArgs mel{x, (long)d, 0, w_mel, b_mel, nullptr, 0, nullptr, nullptr, ys + n_mels, (long)ld_ys, (long)n_mels, nullptr, 0, 0,
-                   n_mels, B, n_mels, d, TTTS_ACT_NONE, st};
-    int rc = check_decode_linear(mel, "decode_frame_out (mel head)");
+                   n_mels, B, n_mels, d, TTTS_ACT_NONE, st, row_end};
+    char name[96];
+    snprintf(name, sizeof name, "%s (mel head)", what);
+    int rc = check_decode_linear(mel, name);
     if (rc != TTTS_OK) return rc;
     rc = launch_decode_linear(mel, (hipStream_t)stream);
     if (rc != TTTS_OK) return rc;
-    const int kc = cdiv(d, 256);
-    hipStream_t s = (hipStream_t)stream;
-    if (kc <= 1) hipLaunchKernelGGL(decode_stop_kernel<1>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, (long)ld_stop, B, d, st);
-    else if (kc <= 2) hipLaunchKernelGGL(decode_stop_kernel<2>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, (long)ld_stop, B, d, st);
-    else if (kc <= 4) hipLaunchKernelGGL(decode_stop_kernel<4>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, (long)ld_stop, B, d, st);
-    else if (kc <= 8) hipLaunchKernelGGL(decode_stop_kernel<8>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, (long)ld_stop, B, d, st);
-    else hipLaunchKernelGGL(decode_stop_kernel<16>, dim3(1), dim3(256), 0, s, x, w_stop, b_stop, stop, (long)ld_stop, B, d, st);
-    TTTS_LAUNCH_CHECK("decode_frame_out");
+    launch_decode_stop(x, w_stop, b_stop, stop, (long)ld_stop, B, d, row_end, st, (hipStream_t)stream);
+    TTTS_LAUNCH_CHECK(what);
     return TTTS_OK;
+}
+
+static int decode_layernorm_impl(const char* what, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
+                                 float eps, const int64_t* row_end, const ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(x && gamma && beta && y && st, "%s: null pointer", what);
+    TTTS_REQUIRE(M >= 1 && d >= 1 && d <= 64 * LN_PER && M <= 4 * 65535, "%s: bad sizes M=%d d=%d (d <= %d)", what, M, d,
+                 64 * LN_PER);
+    hipLaunchKernelGGL(decode_layernorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, M, d, eps,
+                       row_end, st);
+    TTTS_LAUNCH_CHECK(what);
+    return TTTS_OK;
+}
+
+int ttts_decode_linear(const float* x, int64_t ldx, int64_t x_tstride, const float* w, const float* bias, const float* residual,
+                       int64_t ldr, float* y, int64_t ldy, int64_t y_tstride, float* y2, int64_t ldy2, int64_t y2_tstride,
+                       int n_split, int M, int N, int K, int act, const ttts_decode_state* st, void* stream) {
+    return decode_linear_impl("decode_linear", x, ldx, x_tstride, w, bias, residual, ldr, y, ldy, y_tstride, y2, ldy2, y2_tstride,
+                              n_split, M, N, K, act, nullptr, st, stream);
+}
+
+int ttts_decode_linear_rows(const float* x, int64_t ldx, int64_t x_tstride, const float* w, const float* bias,
+                            const float* residual, int64_t ldr, float* y, int64_t ldy, int64_t y_tstride, float* y2, int64_t ldy2,
+                            int64_t y2_tstride, int n_split, int M, int N, int K, int act, const int64_t* row_end,
+                            const ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(row_end, "decode_linear_rows: null pointer (row_end)");
+    return decode_linear_impl("decode_linear_rows", x, ldx, x_tstride, w, bias, residual, ldr, y, ldy, y_tstride, y2, ldy2,
+                              y2_tstride, n_split, M, N, K, act, row_end, st, stream);
+}
+
+int ttts_decode_frame_in(const float* ys, int64_t ld_ys, int n_mels, const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* pe, const float* alpha, float* tmp, float* out, int B, int d,
+                         const ttts_decode_state* st, void* stream) {
+    return decode_frame_in_impl("decode_frame_in", ys, ld_ys, n_mels, w1, b1, w2, b2, pe, alpha, tmp, out, B, d, nullptr, st, stream);
+}
+
+int ttts_decode_frame_in_rows(const float* ys, int64_t ld_ys, int n_mels, const float* w1, const float* b1, const float* w2,
+                              const float* b2, const float* pe, const float* alpha, float* tmp, float* out, int B, int d,
+                              const int64_t* row_end, const ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(row_end, "decode_frame_in_rows: null pointer (row_end)");
+    return decode_frame_in_impl("decode_frame_in_rows", ys, ld_ys, n_mels, w1, b1, w2, b2, pe, alpha, tmp, out, B, d, row_end, st,
+                                stream);
+}
+
+int ttts_decode_frame_out(const float* x, const float* w_mel, const float* b_mel, const float* w_stop, const float* b_stop,
+                          float* ys, int64_t ld_ys, float* stop, int64_t ld_stop, int B, int d, int n_mels,
+                          ttts_decode_state* st, void* stream) {
+    return decode_frame_out_impl("decode_frame_out", x, w_mel, b_mel, w_stop, b_stop, ys, ld_ys, stop, ld_stop, B, d, n_mels,
+                                 nullptr, st, stream);
+}
+
+int ttts_decode_frame_out_rows(const float* x, const float* w_mel, const float* b_mel, const float* w_stop, const float* b_stop,
+                               float* ys, int64_t ld_ys, float* stop, int64_t ld_stop, int B, int d, int n_mels, int64_t* row_end,
+                               ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(row_end, "decode_frame_out_rows: null pointer (row_end)");
+    return decode_frame_out_impl("decode_frame_out_rows", x, w_mel, b_mel, w_stop, b_stop, ys, ld_ys, stop, ld_stop, B, d, n_mels,
+                                 row_end, st, stream);
 }
 
 int ttts_decode_layernorm(const float* x, const float* gamma, const float* beta, float* y, int M, int d, float eps,
                           const ttts_decode_state* st, void* stream) {
-    TTTS_REQUIRE(x && gamma && beta && y && st, "decode_layernorm: null pointer");
-    TTTS_REQUIRE(M >= 1 && d >= 1 && d <= 64 * LN_PER && M <= 4 * 65535, "decode_layernorm: bad sizes M=%d d=%d (d <= %d)", M, d,
-                 64 * LN_PER);
-    hipLaunchKernelGGL(decode_layernorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, M, d, eps, st);
-    TTTS_LAUNCH_CHECK("decode_layernorm");
-    return TTTS_OK;
+    return decode_layernorm_impl("decode_layernorm", x, gamma, beta, y, M, d, eps, nullptr, st, stream);
+}
+
+int ttts_decode_layernorm_rows(const float* x, const float* gamma, const float* beta, float* y, int M, int d, float eps,
+                               const int64_t* row_end, const ttts_decode_state* st, void* stream) {
+    TTTS_REQUIRE(row_end, "decode_layernorm_rows: null pointer (row_end)");
+    return decode_layernorm_impl("decode_layernorm_rows", x, gamma, beta, y, M, d, eps, row_end, st, stream);
 }
 
 size_t ttts_decode_attention_workspace_bytes(int B, int H, int head_dim, int max_keys) {
@@ -438,31 +653,41 @@ size_t ttts_decode_attention_workspace_bytes(int B, int H, int head_dim, int max
 int ttts_decode_attention(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
                           const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
                           int max_keys, const ttts_decode_state* st, void* stream) {
-    TTTS_REQUIRE(q && k && v && out && ws && st, "decode_attention: null pointer");
-    TTTS_REQUIRE(B >= 1 && H >= 1 && B <= 65535 && H <= 65535 && max_keys >= 1,
-                 "decode_attention: bad sizes B=%d H=%d max_keys=%d", B, H, max_keys);
-    TTTS_REQUIRE(head_dim >= 16 && head_dim <= 128 && head_dim % 16 == 0,
-                 "decode_attention: head_dim=%d (a multiple of 16 up to 128)", head_dim);
-    TTTS_REQUIRE(ldq % 4 == 0 && ld_row % 4 == 0 && ld_batch % 4 == 0 && ldq >= (int64_t)H * head_dim && ld_row >= (int64_t)H * head_dim &&
-                 ld_batch >= 0 && ldo >= (int64_t)H * head_dim,
-                 "decode_attention: strides ldq=%ld ld_row=%ld ld_batch=%ld ldo=%ld (multiples of 4, >= H * head_dim)", (long)ldq,
-                 (long)ld_row, (long)ld_batch, (long)ldo);
-    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)ws) & 15) == 0,
-                 "decode_attention: q, k, v and ws must be 16-byte aligned");
-    TTTS_REQUIRE(ws_bytes >= ttts_decode_attention_workspace_bytes(B, H, head_dim, max_keys),
-                 "decode_attention: workspace of %zu bytes < %zu", ws_bytes, ttts_decode_attention_workspace_bytes(B, H, head_dim, max_keys));
-    hipStream_t s = (hipStream_t)stream;
-    switch (head_dim) {
-        case 16: launch_decode_attention_t<16>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        case 32: launch_decode_attention_t<32>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        case 48: launch_decode_attention_t<48>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        case 64: launch_decode_attention_t<64>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        case 80: launch_decode_attention_t<80>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        case 96: launch_decode_attention_t<96>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        case 112: launch_decode_attention_t<112>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-        default: launch_decode_attention_t<128>(q, ldq, k, v, ld_row, ld_batch, lens, out, ldo, ws, B, H, max_keys, st, s); break;
-    }
-    TTTS_LAUNCH_CHECK("decode_attention");
+    const AttnArgs a{q, k, v, (long)ldq, (long)ld_row, (long)ld_batch, lens, out, (long)ldo, ws, B, H, max_keys, nullptr,
+                     AttnMap{nullptr, 0, 0, 0}, st};
+    const int rc = check_decode_attention(a, head_dim, ws_bytes, "decode_attention");
+    if (rc != TTTS_OK) return rc;
+    return launch_decode_attention(a, head_dim, (hipStream_t)stream, "decode_attention");
+}
+
+int ttts_decode_attention_rows(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
+                               const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
+                               int max_keys, const int64_t* row_end, float* map, int64_t map_ld_head, int64_t map_ld_row,
+                               int map_rows, const ttts_decode_state* st, void* stream) {
+    const AttnArgs a{q, k, v, (long)ldq, (long)ld_row, (long)ld_batch, lens, out, (long)ldo, ws, B, H, max_keys, row_end,
+                     AttnMap{map, (long)map_ld_head, (long)map_ld_row, map_rows}, st};
+    TTTS_REQUIRE(row_end, "decode_attention_rows: null pointer (row_end)");
+    const int rc = check_decode_attention(a, head_dim, ws_bytes, "decode_attention_rows");
+    if (rc != TTTS_OK) return rc;
+    TTTS_REQUIRE(map == nullptr || (map_rows >= 1 && map_ld_row >= max_keys && map_ld_head >= (int64_t)map_rows * map_ld_row),
+                 "decode_attention_rows: map of %d rows, ld_row=%ld ld_head=%ld (rows >= 1, ld_row >= max_keys=%d, ld_head >= "
+                 "rows * ld_row)", map_rows, (long)map_ld_row, (long)map_ld_head, max_keys);
+    return launch_decode_attention(a, head_dim, (hipStream_t)stream, "decode_attention_rows");
+}
+
+int ttts_mask_rows(float* x, const int64_t* lens, int64_t outer, int group, int64_t T, int64_t C, void* stream) {
+    TTTS_REQUIRE(x && lens, "mask_rows: null pointer");
+    TTTS_REQUIRE(outer >= 1 && outer <= 65535 && group >= 1 && T >= 1 && C >= 1,
+                 "mask_rows: bad sizes outer=%ld group=%d T=%ld C=%ld (1 <= outer <= 65535)", (long)outer, group, (long)T, (long)C);
+    TTTS_REQUIRE(((uintptr_t)x & 3) == 0, "mask_rows: x must be 4-byte aligned");
+    const long total = (long)T * C;
+    const int blocks = (int)(total / 1024 < 1 ? 1 : (total / 1024 > 64 ? 64 : total / 1024));
+    const dim3 grid(blocks, (unsigned)outer);
+    if (C % 4 == 0 && ((uintptr_t)x & 15) == 0)
+        hipLaunchKernelGGL(mask_rows_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, lens, group, (long)T, (long)C);
+    else
+        hipLaunchKernelGGL(mask_rows_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, lens, group, (long)T, (long)C);
+    TTTS_LAUNCH_CHECK("mask_rows");
     return TTTS_OK;
 }
 

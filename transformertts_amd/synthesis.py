@@ -2,6 +2,7 @@
 
     synth = Synthesizer(model)
     out = synth(phoneme, phoneme_lens, max_len=1500, stop_threshold=0.5)     # the dict model.inference(...) returns
+    out = synth.synthesize(phoneme, phoneme_lens, max_len=1500, stop_threshold=0.5, alignments=False)   # each row at its own length
 
 Same semantics as the reference's `inference` (model/model.py:323-394) and as `TransformerTTS.inference`: eval mode (the model
 is left in it), the encoder runs without a padding mask, cross-attention is masked by `phoneme_lens`, decoding stops at the
@@ -20,6 +21,15 @@ Graphs and their static buffers are cached per (B, Tp rounded up to 64, capacity
 used evicted beyond `max_shapes`.  The kernels read the parameters' own storage, so in-place updates (`load_state_dict`,
 FlatAdam, `.data` writes into the same storage) are seen by the next call; a parameter whose storage moved (replaced, or the
 module moved) makes the next call drop the graphs and capture again.
+
+`synthesize` is the batched form a caller of a TTS engine wants: every utterance ends at ITS first frame at or above the
+threshold (that frame is kept), the call ends when the last one has, and the dict carries `mel_lens` and exact zeros behind
+each row's end.  The per-row end frames live in a device array right behind the decode state (one copy resets both), and the
+kernels skip the rows that have ended.  A cached shape holds up to three chunk graphs over the same buffers, each captured the
+first time it is needed: `__call__`'s (the entry points without per-row state: reading it costs every kernel a little, which
+`__call__` does not pay), `synthesize`'s, and `synthesize(alignments=True)`'s, whose cross-attention kernels are the
+map-writing variant; the map buffers are allocated with that capture.  Within a method, `max_len`, the threshold and where the
+rows stop are data: they never cause a capture.
 """
 from __future__ import annotations
 
@@ -34,6 +44,7 @@ _CAPTURE_MODE = "thread_local"      # as step.py: illegal-during-capture checks 
 _TP_ROUND = 64
 _CAP_ROUND = 256
 _ACT_NONE, _ACT_RELU = 0, 1
+_PER_ROW = 1                        # TTTS_DECODE_PER_ROW
 
 
 def _up(x: int, m: int) -> int:
@@ -55,7 +66,8 @@ class _Shape:
         nm = model.n_mels
         f32 = dict(dtype=torch.float32, device=dev)
         self.B, self.Tp_pad, self.cap = B, Tp_pad, cap
-        self.state = torch.zeros(4, dtype=torch.int64, device=dev)          # ttts_decode_state (32 bytes)
+        # ttts_decode_state (32 bytes), then row_end (B entries, allocated up to a multiple of 4 as the kernels read it)
+        self.state = torch.zeros(4 + _up(B, 4), dtype=torch.int64, device=dev)
         self.ys = torch.zeros(B, cap, nm, **f32)                             # frame 0 (the go frame) stays zero
         self.stop = torch.zeros(B, cap, **f32)
         self.h = torch.zeros(B, d, **f32)
@@ -70,12 +82,21 @@ class _Shape:
         self.ws_bytes = max(lib.ttts_decode_attention_workspace_bytes(B, H, d // H, cap),
                             lib.ttts_decode_attention_workspace_bytes(B, H, d // H, Tp_pad))
         self.ws = torch.zeros(max(self.ws_bytes // 4, 4), **f32)
-        self.calls = None
-        self.graph = None
+        self.maps = None                                                     # per layer (B, H, cap, Tp_pad), once asked for
+        self._map_shape = (B, H, cap, Tp_pad)
+        self.drop_graphs()
+
+    def drop_graphs(self):
+        self.calls = {}                               # keyed by the mode of Synthesizer._frame_calls
+        self.graph = {}
+
+    def alloc_maps(self, n_layers: int):
+        if self.maps is None:
+            self.maps = [torch.zeros(*self._map_shape, dtype=torch.float32, device=self.state.device) for _ in range(n_layers)]
 
     def nbytes(self) -> int:
         ts = [self.state, self.ys, self.stop, self.h, self.tmp, self.q, self.ctx, self.ffn, self.lens, self.ws]
-        return sum(t.numel() * t.element_size() for t in ts + self.cache + self.memkv)
+        return sum(t.numel() * t.element_size() for t in ts + self.cache + self.memkv + (self.maps or []))
 
 
 class Synthesizer:
@@ -93,7 +114,8 @@ class Synthesizer:
         self._shapes: "OrderedDict[tuple, _Shape]" = OrderedDict()
         self._weights_sig = None
         self._side = None
-        self.captures = 0            # chunk graphs captured so far (a shape's first call, or after its weights moved)
+        self.captures = 0            # chunk graphs captured so far (per shape: the first __call__, the first synthesize, the
+        #                              first synthesize with alignments; and again after its weights moved)
         self.recaptures = 0          # times moved parameter storage dropped the captured graphs
 
     @property
@@ -102,7 +124,7 @@ class Synthesizer:
         return self._chunk
 
     def shape_bytes(self) -> dict:
-        """static-buffer footprint of every cached shape, {(B, Tp_pad, cap): bytes}"""
+        """static-buffer footprint of every cached shape (alignment maps included once allocated), {(B, Tp_pad, cap): bytes}"""
         return {k: s.nbytes() for k, s in self._shapes.items()}
 
     # ------------------------------------------------------------------------------------------------------ checks
@@ -147,8 +169,7 @@ class Synthesizer:
         sig = tuple(t.data_ptr() for t in self._weight_tensors())
         if self._weights_sig is not None and sig != self._weights_sig:
             for s in self._shapes.values():
-                s.graph = None
-                s.calls = None
+                s.drop_graphs()
             self.recaptures += 1
         self._weights_sig = sig
 
@@ -166,8 +187,10 @@ class Synthesizer:
         self._shapes.move_to_end(key)
         return self._shapes[key]
 
-    def _frame_calls(self, sh: _Shape):
-        """the launch sequence of one frame: [(entry point, arguments without the stream)]"""
+    def _frame_calls(self, sh: _Shape, mode: str):
+        """the launch sequence of one frame: [(entry point, arguments without the stream)].  `mode` "call": the entry points
+        without per-row state (no row ever ends); "rows": the *_rows entry points on the shape's row_end; "maps": those, with
+        cross-attention also writing row t - 1 of every layer's alignment map"""
         lib = _lib.load()
         m = self.model
         layers = list(m.decoder.layers)
@@ -177,52 +200,62 @@ class Synthesizer:
         hd = d // H
         d_ffn = layers[0].linear1.weight.shape[0]
         st = _ptr(sh.state)
+        rows = mode != "call"
+        re = (_ptr(sh.state, 8),) if rows else ()    # row_end: behind the 32 bytes of the state
+        f_in, f_lin, f_ln, f_att, f_out = ((lib.ttts_decode_frame_in_rows, lib.ttts_decode_linear_rows,
+                                            lib.ttts_decode_layernorm_rows, lib.ttts_decode_attention_rows,
+                                            lib.ttts_decode_frame_out_rows) if rows else
+                                           (lib.ttts_decode_frame_in, lib.ttts_decode_linear, lib.ttts_decode_layernorm,
+                                            lib.ttts_decode_attention, lib.ttts_decode_frame_out))
         h, tmp, q, ctx, ffn, ws = _ptr(sh.h), _ptr(sh.tmp), _ptr(sh.q), _ptr(sh.ctx), _ptr(sh.ffn), _ptr(sh.ws)
         p1, p2 = m.dec_prenet.linear1.linear, m.dec_prenet.linear2.linear
-        calls = [(lib.ttts_decode_frame_in, (_ptr(sh.ys), cap * nm, nm, _ptr(p1.weight), _ptr(p1.bias), _ptr(p2.weight),
-                                             _ptr(p2.bias), _ptr(m.pe.pe), _ptr(m.pe.alpha), tmp, h, B, d, st))]
+        calls = [(f_in, (_ptr(sh.ys), cap * nm, nm, _ptr(p1.weight), _ptr(p1.bias), _ptr(p2.weight), _ptr(p2.bias), _ptr(m.pe.pe),
+                         _ptr(m.pe.alpha), tmp, h, B, d, *re, st))]
 
         def linear(x, K, w, b, y, N, res=None, act=_ACT_NONE):
-            return (lib.ttts_decode_linear, (x, K, 0, _ptr(w), _ptr(b), res, d if res is not None else 0, y, N, 0, None, 0, 0,
-                                             N, B, N, K, act, st))
+            return (f_lin, (x, K, 0, _ptr(w), _ptr(b), res, d if res is not None else 0, y, N, 0, None, 0, 0, N, B, N, K, act,
+                            *re, st))
 
-        for l, cache, mkv in zip(layers, sh.cache, sh.memkv):
+        def norm(n):
+            return (f_ln, (tmp, _ptr(n.weight), _ptr(n.bias), h, B, d, n.eps, *re, st))
+
+        for i, (l, cache, mkv) in enumerate(zip(layers, sh.cache, sh.memkv)):
             sa, ca = l.self_attn, l.multihead_attn
+            no_map = (*re, None, 0, 0, 0) if rows else ()
+            amap = (*re, _ptr(sh.maps[i]), cap * sh.Tp_pad, sh.Tp_pad, cap) if mode == "maps" else no_map
             # in-projection: q to `q`, the K/V columns straight into row t - 1 of this layer's cache
-            calls.append((lib.ttts_decode_linear, (h, d, 0, _ptr(sa.in_proj_weight), _ptr(sa.in_proj_bias), None, 0, q, d, 0,
-                                                   _ptr(cache), cap * 2 * d, 2 * d, d, B, 3 * d, d, _ACT_NONE, st)))
-            calls.append((lib.ttts_decode_attention, (q, d, _ptr(cache), _ptr(cache, d), 2 * d, cap * 2 * d, None, ctx, d, ws,
-                                                      sh.ws_bytes, B, H, hd, cap, st)))
+            calls.append((f_lin, (h, d, 0, _ptr(sa.in_proj_weight), _ptr(sa.in_proj_bias), None, 0, q, d, 0, _ptr(cache),
+                                  cap * 2 * d, 2 * d, d, B, 3 * d, d, _ACT_NONE, *re, st)))
+            calls.append((f_att, (q, d, _ptr(cache), _ptr(cache, d), 2 * d, cap * 2 * d, None, ctx, d, ws, sh.ws_bytes, B, H, hd,
+                                  cap, *no_map, st)))
             calls.append(linear(ctx, d, sa.out_proj.weight, sa.out_proj.bias, tmp, d, res=h))
-            calls.append((lib.ttts_decode_layernorm, (tmp, _ptr(l.norm1.weight), _ptr(l.norm1.bias), h, B, d, l.norm1.eps, st)))
+            calls.append(norm(l.norm1))
             calls.append(linear(h, d, ca.in_proj_weight, ca.in_proj_bias, q, d))          # rows 0 .. d - 1: the q projection
-            calls.append((lib.ttts_decode_attention, (q, d, _ptr(mkv), _ptr(mkv, d), 2 * d, sh.Tp_pad * 2 * d, _ptr(sh.lens), ctx,
-                                                      d, ws, sh.ws_bytes, B, H, hd, sh.Tp_pad, st)))
+            calls.append((f_att, (q, d, _ptr(mkv), _ptr(mkv, d), 2 * d, sh.Tp_pad * 2 * d, _ptr(sh.lens), ctx, d, ws, sh.ws_bytes,
+                                  B, H, hd, sh.Tp_pad, *amap, st)))
             calls.append(linear(ctx, d, ca.out_proj.weight, ca.out_proj.bias, tmp, d, res=h))
-            calls.append((lib.ttts_decode_layernorm, (tmp, _ptr(l.norm2.weight), _ptr(l.norm2.bias), h, B, d, l.norm2.eps, st)))
+            calls.append(norm(l.norm2))
             calls.append(linear(h, d, l.linear1.weight, l.linear1.bias, ffn, d_ffn, act=_ACT_RELU))
             calls.append(linear(ffn, d_ffn, l.linear2.weight, l.linear2.bias, tmp, d, res=h))
-            calls.append((lib.ttts_decode_layernorm, (tmp, _ptr(l.norm3.weight), _ptr(l.norm3.bias), h, B, d, l.norm3.eps, st)))
+            calls.append(norm(l.norm3))
         hm, hs = m.linear1.linear, m.linear2.linear
-        calls.append((lib.ttts_decode_frame_out, (h, _ptr(hm.weight), _ptr(hm.bias), _ptr(hs.weight), _ptr(hs.bias), _ptr(sh.ys),
-                                                  cap * nm, _ptr(sh.stop), cap, B, d, nm, st)))
+        calls.append((f_out, (h, _ptr(hm.weight), _ptr(hm.bias), _ptr(hs.weight), _ptr(hs.bias), _ptr(sh.ys), cap * nm,
+                              _ptr(sh.stop), cap, B, d, nm, *re, st)))
         return calls
 
-    def _run_chunk(self, sh: _Shape, stream: c_void_p):
+    def _run_chunk(self, calls, stream: c_void_p):
         for _ in range(self._chunk):
-            for fn, args in sh.calls:
+            for fn, args in calls:
                 _lib.check(fn(*args, stream), fn.__name__)
 
     def _read_state(self, sh: _Shape):
-        v = sh.state.cpu()             # one small device-to-host read on the side stream (synchronising)
+        v = sh.state[:4].cpu()         # one 32-byte device-to-host read on the side stream (synchronising)
         return int(v[0]), int(v[2])
 
     # ------------------------------------------------------------------------------------------------------ the call
-    @torch.no_grad()
-    def __call__(self, phoneme: torch.Tensor, phoneme_lens: torch.Tensor, max_len: int = 1500,
-                 stop_threshold: float = 0.5) -> dict:
-        self._check_call(phoneme, phoneme_lens, max_len)
-        max_len = int(max_len)
+    def _decode(self, phoneme, phoneme_lens, max_len: int, stop_threshold: float, mode: str):
+        """encoder, memory K/V, then the chunk graph of `mode` until the state says the decoding has ended: (shape, frames
+        decoded)"""
         m = self.model
         m.eval()
         self._follow_weights()
@@ -239,37 +272,100 @@ class Synthesizer:
             kv = ops.linear(memory, ops.param_rows(ca.in_proj_weight, d, 3 * d), ops.param_rows(ca.in_proj_bias, d, 3 * d))
             buf[:, :Tp].copy_(kv)
         sh.lens.copy_(phoneme_lens.to(torch.int64))
-        host = torch.tensor([1, max_len, -1, 0], dtype=torch.int64)
+        host = torch.full((sh.state.numel(),), -1, dtype=torch.int64)        # every row running
+        host[0], host[1], host[3] = 1, max_len, 0
         host.view(torch.float32)[6] = float(stop_threshold)
+        host.view(torch.int32)[7] = _PER_ROW if mode != "call" else 0
         sh.state.copy_(host)
-        if sh.calls is None:
-            sh.calls = self._frame_calls(sh)
+        if mode == "maps":
+            sh.alloc_maps(len(layers))
+        if sh.calls.get(mode) is None:
+            sh.calls[mode] = self._frame_calls(sh, mode)
+        calls = sh.calls[mode]
         if self._side is None or self._side.device != dev:
             self._side = torch.cuda.Stream(device=dev)
         side = self._side
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             stream = c_void_p(side.cuda_stream)
-            if sh.graph is None:
-                self._run_chunk(sh, stream)                  # the shape's first frames run eagerly ...
+            if sh.graph.get(mode) is None:
+                self._run_chunk(calls, stream)               # the shape's first frames run eagerly ...
                 g = torch.cuda.CUDAGraph()
                 g.capture_begin(capture_error_mode=_CAPTURE_MODE)
                 try:
-                    self._run_chunk(sh, stream)              # ... then the same launches are captured (not run)
+                    self._run_chunk(calls, stream)           # ... then the same launches are captured (not run)
                 finally:
                     g.capture_end()
-                sh.graph = g
+                sh.graph[mode] = g
                 self.captures += 1
             t, stop_frame = self._read_state(sh)
             while stop_frame < 0 and t < max_len:
-                sh.graph.replay()
+                sh.graph[mode].replay()
                 t, stop_frame = self._read_state(sh)
         torch.cuda.current_stream(dev).wait_stream(side)
-        n = stop_frame if stop_frame >= 0 else max_len - 1
+        return sh, (stop_frame if stop_frame >= 0 else max_len - 1)
+
+    @torch.no_grad()
+    def __call__(self, phoneme: torch.Tensor, phoneme_lens: torch.Tensor, max_len: int = 1500,
+                 stop_threshold: float = 0.5) -> dict:
+        self._check_call(phoneme, phoneme_lens, max_len)
+        m = self.model
+        sh, n = self._decode(phoneme, phoneme_lens, int(max_len), stop_threshold, "call")
         pred = sh.ys[:, 1:n + 1].clone()
         stops = sh.stop[:, :n].clone().unsqueeze(-1)
         post = ops.AddFn.apply(m.postnet(pred), pred)
         return {'pred_melspec': pred, 'post_melspec': post, 'pred_stop': stops}
+
+    @torch.no_grad()
+    def synthesize(self, phoneme: torch.Tensor, phoneme_lens: torch.Tensor, max_len: int = 1500, stop_threshold: float = 0.5,
+                   alignments: bool = False) -> dict:
+        """Every utterance at its own length.  Row b ends at its first frame t (1-based) with sigmoid(stop[b, t - 1]) >=
+        `stop_threshold` -- that frame is kept -- or at `max_len` - 1; the call ends when every row has.  Returns `pred_melspec`,
+        `post_melspec` (B, T, n_mels), `pred_stop` (B, T, 1) with T = mel_lens.max(), `mel_lens` (B,) int64 on the device, and
+        with `alignments=True` one (B, heads, T, Tp) cross-attention map per decoder layer.  Everything at frame >= mel_lens[b]
+        of row b is exactly 0; a row's frames before its end are bit for bit those of `__call__` for that row, and its
+        `post_melspec` is the post-net of its own frames (the rows behind each end are zeroed between the post-net's layers)."""
+        if not isinstance(alignments, bool):
+            raise ValueError(f"Synthesizer: `alignments` must be a bool, got {type(alignments).__name__}")
+        self._check_call(phoneme, phoneme_lens, max_len)
+        m = self.model
+        max_len = int(max_len)
+        sh, n = self._decode(phoneme, phoneme_lens, max_len, stop_threshold, "maps" if alignments else "rows")
+        B, Tp = phoneme.shape
+        row_end = sh.state[4:4 + B]
+        mel_lens = torch.where(row_end > 0, row_end, torch.full_like(row_end, max_len - 1))
+        pred = _mask_rows(sh.ys[:, 1:n + 1].clone(), mel_lens)
+        stops = _mask_rows(sh.stop[:, :n].clone().unsqueeze(-1), mel_lens)
+        x = pred
+        for conv, act in _postnet_layers(m.postnet):
+            x = _mask_rows(conv.fused(x, act, 0.0), mel_lens)          # (eval mode: the post-net's dropout is off)
+        post = ops.AddFn.apply(x, pred)
+        out = {'pred_melspec': pred, 'post_melspec': post, 'pred_stop': stops, 'mel_lens': mel_lens}
+        if alignments:
+            out['alignments'] = [_mask_rows(a[:, :, :n, :Tp].clone(), mel_lens) for a in sh.maps]
+        return out
+
+
+def _mask_rows(x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """x (B, T, C) or (B, H, T, C), fresh and contiguous: rows t >= lens[b] := 0, in place"""
+    if not (x.is_contiguous() and x.dtype == torch.float32):
+        raise RuntimeError("Synthesizer: masking expects a contiguous fp32 tensor")
+    group = x.shape[1] if x.dim() == 4 else 1
+    lib = _lib.load()
+    _lib.check(lib.ttts_mask_rows(_ptr(x), c_void_p(lens.data_ptr()), x.shape[0] * group, group, x.shape[-2], x.shape[-1],
+                                  ops._stream()), "ttts_mask_rows")
+    return x
+
+
+def _postnet_layers(postnet):
+    """[(ConvNormBN, activation)] in the order PostNet.forward runs them"""
+    mods = list(postnet.layers)
+    out = []
+    for i, mod in enumerate(mods):
+        if hasattr(mod, "fused"):
+            tanh = i + 1 < len(mods) and isinstance(mods[i + 1], torch.nn.Tanh)
+            out.append((mod, ops.ACT_TANH if tanh else ops.ACT_NONE))
+    return out
 
 
 def _check_structure(model):
