@@ -61,6 +61,15 @@ CONFIGS = {
         decoder_n_head=8, decoder_d_ffn=2048, decoder_dropout=0.1,
         postnet_n_layers=5, postnet_kernel_size=5, postnet_dropout=0.5,
         d_model=512, n_phon=100, n_mels=80),
+    # the widest model the decode kernels advertise (d_model 1024, d_ffn 4096, head_dim 128), one layer each side
+    "wide": dict(
+        encoder_prenet_n_layers=1, encoder_prenet_in_channel=1024,
+        encoder_prenet_out_channel=1024, encoder_prenet_kernel_size=5,
+        encoder_prenet_dropout=0.5, encoder_n_layers=1, encoder_n_head=8,
+        encoder_d_ffn=4096, encoder_dropout=0.1, decoder_n_layers=1,
+        decoder_n_head=8, decoder_d_ffn=4096, decoder_dropout=0.1,
+        postnet_n_layers=2, postnet_kernel_size=5, postnet_dropout=0.5,
+        d_model=1024, n_phon=100, n_mels=80),
 }
 
 
