@@ -73,6 +73,26 @@ def test_linear_go_frame_shift():
     assert rel_l2(bg.grad, bd.grad) < TOL
 
 
+@pytest.mark.parametrize("M,N,K,act,res", [(300, 130, 256, 0, False), (4099, 1026, 256, 1, False), (513, 130, 1024, 0, True)])
+def test_linear_forward_on_the_bf16x6_shape_fallback(M, N, K, act, res):
+    """An output width that is no multiple of 4: the fp16x3 kernels do not take it (ops._h3_shape_ok) and ops.linear launches
+    the bf16x6 form instead -- the only launches of ops that are not fp16x3.  Forward only: the library's data-gradient and
+    weight-gradient entry points reject such a width in every form (multiples of 16 resp. 4), so no such layer can train.
+    Same fp64 reference and TOL as test_linear_fwd_bwd."""
+    from transformertts_amd import ops
+    assert N % 4 != 0 and K % 16 == 0          # (bf16x6 images hold whole 16-deep k-tiles)
+    x, w, b = _rand(M, K, seed=1), _rand(N, K, seed=2, scale=K ** -0.5), _rand(N, seed=3, scale=0.1)
+    r = _rand(M, N, seed=4) if res else None
+    ref = F.linear(x.double(), w.double(), b.double())
+    if act:
+        ref = F.relu(ref)
+    if res:
+        ref = ref + r.double()
+    with torch.no_grad():
+        y = ops.linear(x.to(_dev()), w.to(_dev()), b.to(_dev()), residual=r.to(_dev()) if res else None, act=act)
+    assert rel_l2(y, ref) < TOL
+
+
 @pytest.mark.parametrize("B,T,cin,cout,act,training", [(3, 37, 128, 128, 0, True), (2, 300, 80, 256, 2, True),
                                                         (2, 131, 256, 80, 0, True), (4, 50, 256, 256, 2, True),
                                                         (2, 64, 256, 256, 2, False), (5, 1, 16, 128, 2, True),

@@ -181,12 +181,12 @@ class TransformerTTS(nn.Module):
 
     def twin_encode_ok(self, phoneme: Tensor) -> bool:
         """can `encode_twin` serve this model?  (64-column heads: the encoder's attention then runs on head images, the only form
-        the twin batch takes; fp16x3 forms selected; training mode -- in eval mode there is one forward)"""
+        the twin batch takes; training mode -- in eval mode there is one forward)"""
         d = self.emb.weight.shape[1]
         layers = list(self.encoder.layers)
         return (ops.TWIN_ENCODER and self.training and phoneme.is_cuda and len(layers) > 0 and self.encoder.norm is None and
                 all(l.self_attn.embed_dim == d and d == l.self_attn.num_heads * 64 and not l.norm_first for l in layers) and
-                ops.HEAD_IMAGES and ops.ATTN_FWD_MODE == "h3" and ops.ATTN_BWD_MODE == "h3" and ops._fwd_h3(d, 3 * d) and
+                ops.HEAD_IMAGES and ops._h3_shape_ok(d, 3 * d) and
                 2 * phoneme.numel() * 3 * d * 4 < (1 << 31))
 
     def twin_postnet_ok(self, melspec: Tensor) -> bool:
@@ -194,7 +194,7 @@ class TransformerTTS(nn.Module):
         has no batch statistics to keep apart and there is one forward), fp16x3 convolutions throughout."""
         convs = [m for m in self.postnet.layers if hasattr(m, "conv")]
         return (ops.TWIN_POSTNET and self.training and melspec.is_cuda and len(convs) > 0 and
-                all(ops._fwd_h3(c.conv.weight.shape[2] * c.conv.weight.shape[1], c.conv.weight.shape[0], c.conv.weight.shape[1])
+                all(ops._h3_shape_ok(c.conv.weight.shape[2] * c.conv.weight.shape[1], c.conv.weight.shape[0], c.conv.weight.shape[1])
                     for c in convs) and 2 * melspec.shape[0] * melspec.shape[1] * max(c.conv.weight.shape[0] for c in convs) * 4 < (1 << 31))
 
     def encode_twin(self, phoneme: Tensor, phoneme_lens: Tensor):

@@ -211,64 +211,20 @@ def _ss():
     """`step_seed` / `ttts_step_state*` argument of the C ABI: the active StepState block, or NULL."""
     return None if _active_state is None else _active_state.ptr
 
-# Forward / data-gradient GEMMs and convolutions: "x6" = fp32-accurate split-precision products on the bf16 MFMA
-# (3-way bf16 split, six MFMA terms, fp32 accumulate; error 1.1e-7 vs 2.9e-7 for the plain fp32 MFMA chain),
-# "f32" = the plain v_mfma_f32_32x32x2_f32 kernel.  Weight gradients always use the fp32 kernel.
-GEMM_MODE = "x6"
-ATTN_MODE = GEMM_MODE       # attention products (backward; forward unless ATTN_FWD_MODE): "x6" or "f32"
-ATTN_FWD_MODE = "h3"   # forward: "h3", "x6", "f32"
-ATTN_BWD_MODE = "h3"   # backward: "h3", "x6", "f32"
-WGRAD_MODE = "h3"   # weight gradients: "h3", "x6", "f32"
-# Forward GEMMs (nn.Linear / Conv1d forward) under GEMM_MODE "x6": "h3" = fp16x3 split (three f16 MFMA terms, both operands
-# pre-scaled by powers of two taken from their MEASURED maxima, csrc/gemm_h3.hip -- no magnitude window), "x6" = bf16x6.
-# Shapes the fp16 kernel cannot take (K or channels not a multiple of 4) go to bf16x6.
-FWD_MODE = "h3"
 
-
-# Data-gradient GEMMs: "h3" = fp16x3 with a dynamic pre-scale of the gradient operand (one amax pass over dy), "x6".
-BWD_MODE = "h3"
-
-
-class cross_check_forms:
-    """TEST / TOOL API, not configuration: the product path always runs the fp16x3 forms and reads no environment
-    variable.  `with ops.cross_check_forms(gemm="f32")` (or fwd= / bwd= / wgrad= / attn_fwd= / attn_bwd= "x6") routes the
-    launches made inside the block to the bf16x6 / fp32-MFMA forms the library keeps as numerical cross-checks
-    (tests/test_hip_modes.py holds all forms to the same fp64 references); `defer_reduce=False` runs every column reduction
-    as it occurs instead of batching them at the end of backward."""
-
-    _NAMES = {"gemm": "GEMM_MODE", "fwd": "FWD_MODE", "bwd": "BWD_MODE", "wgrad": "WGRAD_MODE", "attn": "ATTN_MODE",
-              "attn_fwd": "ATTN_FWD_MODE", "attn_bwd": "ATTN_BWD_MODE", "defer_reduce": "DEFER_REDUCE",
-              "wgrad_groups": "WGRAD_GROUPS"}
-
-    def __init__(self, **forms):
-        unknown = set(forms) - set(self._NAMES)
-        if unknown:
-            raise TypeError(f"cross_check_forms: unknown form(s) {sorted(unknown)}")
-        if forms.get("gemm") == "f32":         # the fp32-MFMA form of everything, as the old process-wide switch meant it
-            forms = dict({"attn": "f32", "attn_fwd": "f32", "attn_bwd": "f32", "wgrad": "f32"}, **forms)
-        self.forms, self.saved = forms, {}
-
-    def __enter__(self):
-        g = globals()
-        for k, v in self.forms.items():
-            self.saved[k] = g[self._NAMES[k]]
-            g[self._NAMES[k]] = v
-        return self
-
-    def __exit__(self, *exc):
-        g = globals()
-        for k, v in self.saved.items():
-            g[self._NAMES[k]] = v
-
-
-def _fwd_h3(K: int, N: int, channels: int = 0) -> bool:
-    """fp16x3 takes reduction depths, conv channel counts and output widths that are multiples of 4 (the weight image pads
-    the channels of a tap to a multiple of 32 with zeros: ttts_split_image_bytes)."""
-    return GEMM_MODE == "x6" and FWD_MODE == "h3" and K % 4 == 0 and channels % 4 == 0 and N % 4 == 0
-
-
-def _bwd_h3(K: int, N: int, channels: int = 0) -> bool:
-    return GEMM_MODE == "x6" and BWD_MODE == "h3" and K % 4 == 0 and channels % 4 == 0 and N % 4 == 0
+# How fp32 products are formed (DESIGN 4): every GEMM, convolution and attention launched from here runs the fp16x3 form (three
+# f16 MFMA terms, both operands pre-scaled by powers of two taken from their MEASURED maxima, csrc/gemm_h3.hip -- no magnitude
+# window).  The one exception is a shape fallback: a forward or data-gradient GEMM / convolution the fp16x3 kernels do not take
+# (`_h3_shape_ok`) runs as bf16x6 (3-way bf16 split, six MFMA terms), and a weight gradient whose shape the split kernels do not
+# take (`_wgrad_is_split`) runs on the fp32-MFMA kernel inside the library.  There is no switch: the other forms of the library
+# are C entry points that tests/test_hip_modes.py holds to fp64 directly.  Of the four bf16x6 launches only the Linear FORWARD
+# with an output width that is no multiple of 4 can complete today: the bf16x6 entry points want whole 16-deep k-tiles (K, cin
+# resp. N, cout a multiple of 16), so the data gradients and the convolution forward are reached only to be refused by the
+# library (as are the weight gradient and BatchNorm of such a layer: multiples of 4) -- an error, never a wrong result.
+def _h3_shape_ok(K: int, N: int, channels: int = 0) -> bool:
+    """the fp16x3 kernels take this reduction depth, output width and conv channel count: multiples of 4 (the weight image pads
+    the channels of a tap to a multiple of 32 with zeros: ttts_split_image_bytes)"""
+    return K % 4 == 0 and channels % 4 == 0 and N % 4 == 0
 
 
 # ---- guard regions (TEST seam; tests/conftest.py switches it on around every -m gpu test).  The arrays kernels publish into
@@ -399,7 +355,7 @@ def _amax_slots_n(device, n: int) -> torch.Tensor:
 # again, defensively, before a collective over the bucket and before the optimizer reads it.  Nothing is process-global:
 # the queue and its "callback registered" flag belong to the bucket, and `FlatGradBucket.zero()` drops whatever a backward
 # pass that raised (its callback never ran) left behind.
-DEFER_REDUCE = True          # tests flip it through `cross_check_forms(defer_reduce=False)`
+DEFER_REDUCE = True          # False (tests monkeypatch it): every column reduction runs where it occurs
 
 
 WGRAD_GROUPS = True          # small weight gradients of a backward pass run as grouped launches (ReduceQueue.defer_wgrad)
@@ -542,24 +498,44 @@ def _wgrad_is_split(N: int, K: int) -> bool:
 
 
 def _attn_bwd(lib, do, dq_am, dkv_am, q_am, k_am, v_am, rowstat, *args):
-    """Attention backward in the configured form; `args` = every C-ABI argument up to step_seed.  dq_am / dkv_am: zeroed
-    AMAX_SLOTS-slot arrays in which the fp16x3 kernels leave max|dq| / max|dk, dv| (the in-projection gradients consume them);
-    q_am / k_am / v_am: the partial maxima of the forward operands (their dynamic pre-scales)."""
-    if ATTN_BWD_MODE == "h3":
-        return lib.ttts_attention_bwd_h3(*args, _p(_amax(do)), _p(dq_am), _p(dkv_am), _p(q_am), _p(k_am), _p(v_am), _p(rowstat),
-                                         _stream())
-    return (lib.ttts_attention_bwd_x6 if ATTN_BWD_MODE == "x6" else lib.ttts_attention_bwd)(*args, _stream())
+    """Attention backward; `args` = every C-ABI argument up to step_seed.  dq_am / dkv_am: zeroed AMAX_SLOTS-slot arrays in
+    which the kernels leave max|dq| / max|dk, dv| (the in-projection gradients consume them); q_am / k_am / v_am: the partial
+    maxima of the forward operands (their dynamic pre-scales); rowstat: the forward's row statistics (planes 1-3 of `stat`)."""
+    return lib.ttts_attention_bwd_h3(*args, _p(_amax(do)), _p(dq_am), _p(dkv_am), _p(q_am), _p(k_am), _p(v_am), _p(rowstat),
+                                     _stream())
 
 
-def _wgrad(lib, name: str, dy: torch.Tensor, amax, x: torch.Tensor, x_amax, split_ok: bool, queue, *args):
-    """Weight-gradient entry point `name` in the configured form; `args` = everything between (dy, x) and `queue`.
+def _wgrad(lib, name: str, dy: torch.Tensor, amax, x: torch.Tensor, x_amax, queue, N: int, K: int, *args):
+    """Weight-gradient entry point `name` (N outputs, K inputs per tap); `args` = everything between (dy, x) and `queue`.
     The fp16x3 form takes the partial maxima of |dy| and |x| (computed here unless the caller already has them); shapes
-    the split kernels do not take (`split_ok` False) run on the fp32-MFMA kernel behind the _x6 entry point and need none."""
-    if WGRAD_MODE == "h3" and split_ok:
+    the split kernels do not take run on the fp32-MFMA kernel behind the _x6 entry point and need none."""
+    if _wgrad_is_split(N, K):
         am = amax if amax is not None else _amax(dy)
         xm = x_amax if x_amax is not None else _amax(x)
         return getattr(lib, name + "_h3")(_p(dy), _p(x), *args, _p(am), _p(xm), queue, _stream())
-    return getattr(lib, name + ("_x6" if WGRAD_MODE in ("x6", "h3") else ""))(_p(dy), _p(x), *args, queue, _stream())
+    return getattr(lib, name + "_x6")(_p(dy), _p(x), *args, queue, _stream())
+
+
+def _weight_grad(dy, dy_amax, x, x_amax, dw, db, acc: int, queue, M: int, N: int, K: int, taps: int = 1, T: int = 0,
+                 row_shift: int = 0, conv: bool = False) -> None:
+    """dw (+)= dy^T x, db (+)= column sums of dy, taken to its destination: deferred into its group when the destination is
+    a gradient sink with a queue (nobody reads it before the optimizer: `ReduceQueue.defer_wgrad`), launched now otherwise.
+    A Linear's (M rows, N x K weight; `row_shift` / T: the shifted loader) or, `conv`, a convolution's over utterances of T
+    rows (N = cout, K = cin)."""
+    lib = _lib.load()
+    cls = lib.ttts_wgrad_group_ok(M, N, K, taps) if (WGRAD_GROUPS and DEFER_REDUCE and queue is not None and
+                                                     _wgrad_is_split(N, K)) else 0
+    if cls == 2 and row_shift != 0:
+        cls = 0                      # (the LDS-DMA tile clips utterances of at least 16 rows only: keep the checked single launch)
+    if cls:
+        queue.defer_wgrad(cls, dy, dy_amax if dy_amax is not None else _amax(dy), x, x_amax if x_amax is not None else _amax(x),
+                          dw, db, M, N, K, taps, T if (conv or row_shift) else 0, row_shift)
+        return
+    ws = _ws(lib.ttts_wgrad_workspace_bytes(M, N, K, taps), x.device)
+    dims = (M // T, T, K, N, taps) if conv else (M, N, K, row_shift, T)
+    name = "ttts_conv1d_bwd_weight" if conv else "ttts_linear_bwd_weight"
+    _lib.check(_wgrad(lib, name, dy, dy_amax, x, x_amax, _qarg(queue, ws), N, K, _p(dw), _p(db), _p(ws), ws.numel() * 4, *dims, acc),
+               name)
 
 
 _param_epoch = 0
@@ -581,10 +557,18 @@ _plane_entries: list = []        # every (weight, mode) split so far, for the on
 _plane_tables: dict = {}         # flat-storage address -> (signature, device descriptor table, pinned host copy, total blocks)
 
 
+# Weight-image modes of ttts_weight_split (the table of include/ttts_hip.h): which matrix of a weight is laid out, and for
+# which kernel family.  Linear forward = w (N, K), linear data gradient = w^T, conv forward = [co][tap * cin + ci], conv data
+# gradient = [ci][tap * cout + co].
+X6_LIN_FWD, X6_LIN_BWD, X6_CONV_FWD, X6_CONV_BWD = 0, 1, 2, 3      # bf16x6: three bf16 planes (the shape fallback)
+H3_LIN_FWD, H3_LIN_BWD, H3_CONV_FWD, H3_CONV_BWD = 4, 5, 6, 7      # fp16x3: two f16 planes + the scale tail (gemm_h3, conv)
+H3D_LIN_FWD, H3D_LIN_BWD = 8, 9                                    # fp16x3 for the LDS-DMA kernels (h3d / h3i / h3d_img)
+
+
 def _split_units(rows: int, cols: int, mode: int, c2: int) -> int:
     """work units of one entry of the batched refresh; a LINEAR entry's c2 / taps may hold the geometry of a stacked image
     (64-bit packed, `_StackedPlanes`), which is no part of the count"""
-    conv = mode >= 4 and ((mode - 4) & 3) >= 2 or mode in (2, 3)
+    conv = mode in (X6_CONV_FWD, X6_CONV_BWD, H3_CONV_FWD, H3_CONV_BWD)
     return int(_lib.load().ttts_weight_split_units(rows, cols, mode, c2 if conv else 0))
 
 
@@ -823,8 +807,9 @@ DMA_MIN_TILES = 320
 
 def _dma_dims(red: int, out: int) -> bool:
     """could `_dma_shape_ok` say yes for SOME row count?  The choice between the two kernels (and so between the two weight
-    images, modes 4 / 8 resp. 5 / 9) depends on the batch's row count, and a captured graph can only use images that exist:
-    `_both_images` makes both in the eager steps whenever the dimensions are eligible, whatever the current row count."""
+    images, H3_LIN_FWD / H3D_LIN_FWD resp. H3_LIN_BWD / H3D_LIN_BWD) depends on the batch's row count, and a captured graph can
+    only use images that exist: `_both_images` makes both in the eager steps whenever the dimensions are eligible, whatever the
+    current row count."""
     return DMA_GEMMS and red % 32 == 0 and out % 4 == 0 and ((red <= 256 and out >= 512) or (red == out and out in (256, 512)))
 
 
@@ -845,6 +830,74 @@ DMA_BIG_FWD = True          # 256 -> 1024 forward GEMMs (FFN1) on the 256-row LD
 
 def _new_image(M: int, d: int, device):
     return (torch.empty(M * d * 2, dtype=torch.int16, device=device), torch.empty(M, dtype=torch.float32, device=device))
+
+
+_BIAS_ONLY = (ACT_NONE, 0.0, 0, None, 0, 0)
+
+
+def _linear_fwd(x, w, b, r, y, M: int, N: int, K: int, x_amax, y_amax, epi=_BIAS_ONLY, x_image=None, tiles: bool = True):
+    """Launch y = drop(act(x w^T + b)) + r over M rows; -> the partial maxima of x it used (or None).
+    epi = (act, drop_p, seed, step_seed, row_shift, T); x_amax: None = measured here; y_amax: None, or where max|y| goes;
+    x_image: (image, row_inv) of x left by its producer -- the image-operand kernel.  `tiles=False`: no kernel choice here --
+    gemm_h3 on the H3_LIN_FWD image whatever the row count, and no sibling image is made (the mel head)."""
+    lib = _lib.load()
+    if not _h3_shape_ok(K, N):
+        # the shape fallback: K or N no multiple of 4 -- the only launches of ops that are not fp16x3 (with their data
+        # gradient, _linear_bwd_data, and ConvBNFn's two)
+        _lib.check(lib.ttts_linear_fwd_x6(_p(x), _p(_planes(w, X6_LIN_FWD, N, K)), _p(b), _p(r), _p(y), M, N, K, *epi, _stream()),
+                   "ttts_linear_fwd_x6")
+        return x_amax
+    tiles = tiles and epi[4] == 0                      # (the LDS-DMA kernels have no shifted loader)
+    if x_image is not None and tiles:
+        _lib.check(lib.ttts_linear_fwd_h3i(_p(x_image[0]), _p(x_image[1]), _p(_both_images(w, H3D_LIN_FWD, H3_LIN_FWD, N, K)), _p(b),
+                                           _p(r), _p(y), M, N, K, *epi[:4], _p(y_amax), _stream()), "ttts_linear_fwd_h3i")
+        return x_amax
+    if x_amax is None:
+        x_amax = _amax(x)
+    both = tiles and (_dma_dims(K, N) or _image_dims(K, N))
+    if tiles and _dma_shape_ok(M, K, N, False):
+        planes = _both_images(w, H3D_LIN_FWD, H3_LIN_FWD, N, K) if both else _planes(w, H3D_LIN_FWD, N, K)
+        _lib.check(lib.ttts_linear_fwd_h3d(_p(x), _p(planes), _p(b), _p(r), _p(y), M, N, K, *epi[:4], _p(x_amax), _p(y_amax),
+                                           _stream()), "ttts_linear_fwd_h3d")
+    else:
+        planes = _both_images(w, H3_LIN_FWD, H3D_LIN_FWD, N, K) if both else _planes(w, H3_LIN_FWD, N, K)
+        _lib.check(lib.ttts_linear_fwd_h3(_p(x), _p(planes), _p(b), _p(r), _p(y), M, N, K, *epi, _p(x_amax), _p(y_amax), _stream()),
+                   "ttts_linear_fwd_h3")
+    return x_amax
+
+
+def _linear_bwd_data(dy, w, dx, M: int, N: int, K: int, dy_amax, skip=None, gate=None, gscale: float = 1.0, dx_amax=None,
+                     dy_image=None, tiles: bool = True, w_image=None):
+    """Launch dx = (dy w + skip) [* relu mask of `gate` * gscale] over M rows (w: (N, K)); -> the partial maxima of dy it used
+    (or None).  dy_amax: None = measured here; dx_amax: None, or where max|dx| goes; dy_image: (image, row_inv) of dy left by
+    its producer.  `tiles=False`: no kernel choice -- gemm_h3 on the H3_LIN_BWD image, no sibling image (the mel head);
+    `w_image`: that image, ready (the stacked K/V image, whose shape the caller has checked): gemm_h3 on it as it is, `w` is
+    not read and may be None."""
+    lib = _lib.load()
+    assert w is not None or w_image is not None
+    if w_image is None and not _h3_shape_ok(N, K):                  # the shape fallback (see _linear_fwd)
+        _lib.check(lib.ttts_linear_bwd_data_x6(_p(dy), _p(_planes(w, X6_LIN_BWD, K, N)), _p(skip), _p(dx), M, N, K, _p(gate), gscale,
+                                               _stream()), "ttts_linear_bwd_data_x6")
+        return dy_amax
+    tiles = tiles and w_image is None
+    if dy_image is not None and tiles and _image_shape_ok(M, N, K):
+        _lib.check(lib.ttts_linear_bwd_data_h3i(_p(dy_image[0]), _p(dy_image[1]), _p(_both_images(w, H3D_LIN_BWD, H3_LIN_BWD, K, N)),
+                                                _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dx_amax), _stream()),
+                   "ttts_linear_bwd_data_h3i")
+        return dy_amax
+    if dy_amax is None:
+        dy_amax = _amax(dy)
+    both = tiles and (_dma_dims(N, K) or _image_dims(N, K))
+    if tiles and _dma_shape_ok(M, N, K, gate is not None) and not (gate is not None and skip is not None):
+        planes = _both_images(w, H3D_LIN_BWD, H3_LIN_BWD, K, N) if both else _planes(w, H3D_LIN_BWD, K, N)
+        _lib.check(lib.ttts_linear_bwd_data_h3d(_p(dy), _p(planes), _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dy_amax),
+                                                _p(dx_amax), _stream()), "ttts_linear_bwd_data_h3d")
+    else:
+        if w_image is None:
+            w_image = _both_images(w, H3_LIN_BWD, H3D_LIN_BWD, K, N) if both else _planes(w, H3_LIN_BWD, K, N)
+        _lib.check(lib.ttts_linear_bwd_data_h3(_p(dy), _p(w_image), _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dy_amax),
+                                               _p(dx_amax), _stream()), "ttts_linear_bwd_data_h3")
+    return dy_amax
 
 
 class LinearFn(torch.autograd.Function):
@@ -887,30 +940,10 @@ class LinearFn(torch.autograd.Function):
             if x_amax is None:
                 x_amax = _amax(x)
             row_inv, sec_amax, sec_cols = y_himg
-            _lib.check(lib.ttts_linear_fwd_h3d_img(_p(x), _p(_both_images(w, 8, 4, N, K)), _p(b_), _p(y), _p(row_inv), M, N, K, _p(x_amax),
-                                                   _p(sec_amax), sec_cols, _stream()), "ttts_linear_fwd_h3d_img")
-        elif x_image is not None and _fwd_h3(K, N) and row_shift == 0:
-            _lib.check(lib.ttts_linear_fwd_h3i(_p(x_image[0]), _p(x_image[1]), _p(_both_images(w, 8, 4, N, K)), _p(b_), _p(r_), _p(y), M, N, K,
-                                               act, float(drop_p), seed, _ss(), _p(y_amax), _stream()), "ttts_linear_fwd_h3i")
-        elif _fwd_h3(K, N):
-            if x_amax is None:
-                x_amax = _amax(x)
-            both = row_shift == 0 and (_dma_dims(K, N) or _image_dims(K, N))
-            if row_shift == 0 and _dma_shape_ok(M, K, N, False):
-                _lib.check(lib.ttts_linear_fwd_h3d(_p(x), _p(_both_images(w, 8, 4, N, K) if both else _planes(w, 8, N, K)), _p(b_), _p(r_),
-                                                   _p(y), M, N, K, act,
-                                                   float(drop_p), seed, _ss(), _p(x_amax), _p(y_amax), _stream()), "ttts_linear_fwd_h3d")
-            else:
-                _lib.check(lib.ttts_linear_fwd_h3(_p(x), _p(_both_images(w, 4, 8, N, K) if both else _planes(w, 4, N, K)), _p(b_), _p(r_),
-                                                  _p(y), M, N, K, act,
-                                                  float(drop_p), seed, _ss(), row_shift, T, _p(x_amax), _p(y_amax), _stream()),
-                           "ttts_linear_fwd_h3")
-        elif GEMM_MODE == "x6":
-            _lib.check(lib.ttts_linear_fwd_x6(_p(x), _p(_planes(w, 0, N, K)), _p(b_), _p(r_), _p(y), M, N, K, act,
-                                              float(drop_p), seed, _ss(), row_shift, T, _stream()), "ttts_linear_fwd_x6")
+            _lib.check(lib.ttts_linear_fwd_h3d_img(_p(x), _p(_both_images(w, H3D_LIN_FWD, H3_LIN_FWD, N, K)), _p(b_), _p(y), _p(row_inv),
+                                                   M, N, K, _p(x_amax), _p(sec_amax), sec_cols, _stream()), "ttts_linear_fwd_h3d_img")
         else:
-            _lib.check(lib.ttts_linear_fwd(_p(x), _p(w), _p(b_), _p(r_), _p(y), M, N, K, act, float(drop_p), seed,
-                                           _ss(), row_shift, T, _stream()), "ttts_linear_fwd")
+            x_amax = _linear_fwd(x, w, b_, r_, y, M, N, K, x_amax, y_amax, (act, float(drop_p), seed, _ss(), row_shift, T), x_image)
         ctx.save_for_backward(x, w, y if act == ACT_RELU else None)
         ctx.cfg = (act, float(drop_p), seed, row_shift, T, b is not None, residual is not None)
         ctx.sinks = _sinks(w, b)
@@ -934,8 +967,7 @@ class LinearFn(torch.autograd.Function):
         dy = _chk(dy, "linear.dy")
         # partial maxima of |dacc| (dynamic pre-scale of the fp16x3 data / weight gradients): emitted by the mask kernel
         # that produces dacc when there is one, by a separate pass otherwise
-        want_am = (ctx.needs_input_grad[0] and _bwd_h3(N, K)) or \
-                  (ctx.needs_input_grad[1] and WGRAD_MODE == "h3" and _wgrad_is_split(N, K))
+        want_am = (ctx.needs_input_grad[0] and _h3_shape_ok(N, K)) or (ctx.needs_input_grad[1] and _wgrad_is_split(N, K))
         am = None
         dacc_image = None
         if act == ACT_RELU and tok_out is not None and tok_out.premasked:
@@ -971,58 +1003,22 @@ class LinearFn(torch.autograd.Function):
                 skip, skip_in.grad = skip_in.grad, None
                 if skip.shape != x.shape or not skip.is_contiguous():
                     raise RuntimeError("linear: skip-connection gradient does not match the block input")
-            if _bwd_h3(N, K):
-                # dx with the producer's relu mask applied here is exactly the `dacc` of that producer's backward: leave its
-                # maxima on it
-                dx_am = _amax_slots(dx.device, True) if (tok_in is not None or ctx.sole_consumer) else None
-                if dacc_image is not None and _image_shape_ok(M, N, K):
-                    _lib.check(lib.ttts_linear_bwd_data_h3i(_p(dacc_image[0]), _p(dacc_image[1]), _p(_both_images(w, 9, 5, K, N)), _p(skip),
-                                                            _p(dx), M, N, K, _p(gate), gscale, _p(dx_am), _stream()),
-                               "ttts_linear_bwd_data_h3i")
-                else:
-                    am = am if am is not None else _amax(dacc)
-                    both = _dma_dims(N, K) or _image_dims(N, K)
-                    if _dma_shape_ok(M, N, K, gate is not None) and not (gate is not None and skip is not None):
-                        _lib.check(lib.ttts_linear_bwd_data_h3d(_p(dacc), _p(_both_images(w, 9, 5, K, N) if both else _planes(w, 9, K, N)),
-                                                                _p(skip), _p(dx), M, N, K,
-                                                                _p(gate), gscale, _p(am), _p(dx_am), _stream()),
-                                   "ttts_linear_bwd_data_h3d")
-                    else:
-                        _lib.check(lib.ttts_linear_bwd_data_h3(_p(dacc), _p(_both_images(w, 5, 9, K, N) if both else _planes(w, 5, K, N)),
-                                                               _p(skip), _p(dx), M, N, K,
-                                                               _p(gate), gscale, _p(am), _p(dx_am), _stream()),
-                                   "ttts_linear_bwd_data_h3")
-                if dx_am is not None:
-                    dx._ttts_amax = dx_am
-            elif GEMM_MODE == "x6":
-                _lib.check(lib.ttts_linear_bwd_data_x6(_p(dacc), _p(_planes(w, 1, K, N)), _p(skip), _p(dx), M, N, K,
-                                                       _p(gate), gscale, _stream()), "ttts_linear_bwd_data_x6")
-            else:
-                _lib.check(lib.ttts_linear_bwd_data(_p(dacc), _p(w), _p(skip), _p(dx), M, N, K, _p(gate), gscale, _stream()),
-                           "ttts_linear_bwd_data")
+            # dx with the producer's relu mask applied here is exactly the `dacc` of that producer's backward: leave its
+            # maxima on it
+            dx_am = _amax_slots(dx.device, True) if (_h3_shape_ok(N, K) and (tok_in is not None or ctx.sole_consumer)) else None
+            am = _linear_bwd_data(dacc, w, dx, M, N, K, am, skip, gate, gscale, dx_am, dacc_image)
+            if dx_am is not None:
+                dx._ttts_amax = dx_am
             if tok_in is not None:
                 tok_in.premasked = True
         if ctx.needs_input_grad[1]:
             sk, acc, queue = ctx.sinks
-            cls = lib.ttts_wgrad_group_ok(M, N, K, 1) if (WGRAD_GROUPS and DEFER_REDUCE and sk is not None and queue is not None and
-                                                       WGRAD_MODE == "h3" and _wgrad_is_split(N, K)) else 0
-            if cls == 2 and row_shift != 0:
-                cls = 0                      # (the LDS-DMA tile clips utterances of at least 16 rows only: keep the checked single launch)
-            if cls:
-                # an output with a gradient sink: nobody reads it before the optimizer, so it waits for its group
-                queue.defer_wgrad(cls, dacc, am if am is not None else _amax(dacc), x,
-                                  ctx.x_amax if ctx.x_amax is not None else _amax(x), sk[0], sk[1], M, N, K, 1, T if row_shift else 0,
-                                  row_shift)
+            if sk is not None:
+                dw_t, db_t = sk
             else:
-                nbytes = lib.ttts_wgrad_workspace_bytes(M, N, K, 1)
-                ws = _ws(nbytes, x.device)
-                if sk is not None:
-                    dw_t, db_t = sk
-                else:
-                    dw_t = dw = torch.empty_like(w)
-                    db_t = db = torch.empty(N, dtype=torch.float32, device=x.device) if has_b else None
-                _lib.check(_wgrad(lib, "ttts_linear_bwd_weight", dacc, am, x, ctx.x_amax, _wgrad_is_split(N, K), _qarg(queue, ws),
-                                  _p(dw_t), _p(db_t), _p(ws), ws.numel() * 4, M, N, K, row_shift, T, acc), "ttts_linear_bwd_weight")
+                dw_t = dw = torch.empty_like(w)
+                db_t = db = torch.empty(N, dtype=torch.float32, device=x.device) if has_b else None
+            _weight_grad(dacc, am, x, ctx.x_amax, dw_t, db_t, acc, queue, M, N, K, 1, T, row_shift)
         dres = dy if has_r else None
         if has_r and skip_out is not None:      # hand the skip gradient to the block's first Linear instead of autograd
             skip_out.grad, dres = dy, None
@@ -1112,10 +1108,10 @@ class HeadImage:
 
 def head_image_ok(x: torch.Tensor, w: torch.Tensor, n_head: int, sections: int) -> bool:
     """can the in-projection x @ w.T (+ b) leave as a head image for `ops.self_attention` / `cross_attention`?  64-column heads,
-    reduction depth a multiple of 32, the fp16x3 forms selected, operands below 4 GiB."""
+    reduction depth a multiple of 32, operands below 4 GiB."""
     N, K = w.shape
     M = x.numel() // K
-    return (HEAD_IMAGES and x.is_cuda and _fwd_h3(K, N) and ATTN_FWD_MODE == "h3" and ATTN_BWD_MODE == "h3" and K % 32 == 0
+    return (HEAD_IMAGES and x.is_cuda and _h3_shape_ok(K, N) and K % 32 == 0
             and N == sections * n_head * 64 and M * K * 4 < (1 << 32) and (M + 256) * N * 4 < (1 << 32))
 
 
@@ -1130,7 +1126,7 @@ def linear(x, w, b=None, residual=None, act=ACT_NONE, drop_p=0.0, seed=0, row_sh
     maxima to (a running maximum over several calls: the K/V cache of `inference`)."""
     grad_on = torch.is_grad_enabled()
     N, K = w.shape
-    h3 = x.is_cuda and _fwd_h3(K, N)
+    h3 = x.is_cuda and _h3_shape_ok(K, N)
     x_full = _twin(x)
     twin = None
     if x_full is not None:
@@ -1192,8 +1188,8 @@ def _pack2(hi: int, lo: int) -> int:
 
 class _StackedPlanes:
     """ONE fp16x3 weight image of several parameter row slices (all (rows, cols)) STACKED: along the image's rows for the forward
-    image (mode 8: the slices' output columns side by side, N = n * rows) or along its reduction index for the data-gradient
-    image (mode 5: w^T of the slices one behind the other).  Each slice is an ordinary entry of the batched weight refresh
+    image (H3D_LIN_FWD: the slices' output columns side by side, N = n * rows) or along its reduction index for the data-gradient
+    image (H3_LIN_BWD: w^T of the slices one behind the other).  Each slice is an ordinary entry of the batched weight refresh
     (`_plane_entries`, `PlaneTable`) whose descriptor names its window of the shared image (include/ttts_hip.h,
     ttts_weight_split_batched); all windows share the image's tail, i.e. ONE scale from the maximum over every slice.  The
     entries are cached on the parameters the slices were cut from, so the refresh after an optimizer step and the table a
@@ -1204,8 +1200,7 @@ class _StackedPlanes:
         self.mode, self.n = mode, len(slices)
         rows, cols = slices[0].shape
         self.rows, self.cols = rows, cols
-        base = (mode - 4) & 3
-        if base == 0:
+        if mode in (H3_LIN_FWD, H3D_LIN_FWD):
             self.Rimg, self.Cimg = self.n * rows, cols          # forward image: (n rows, cols)
             wins = [(_pack2(self.Rimg, self.Cimg), _pack2(i * rows, 0), rows, cols) for i in range(self.n)]
         else:
@@ -1313,8 +1308,8 @@ class CrossKVProjFn(torch.autograd.Function):
         bias = _stacked_bias(owner, bs)
         if mem_amax is None:
             mem_amax = _amax(mem)
-        planes = _stacked_planes(owner, ws, 8)
-        _stacked_planes(owner, ws, 5)             # the backward's image exists before any capture
+        planes = _stacked_planes(owner, ws, H3D_LIN_FWD)
+        _stacked_planes(owner, ws, H3_LIN_BWD)    # the backward's image exists before any capture
         _lib.check(lib.ttts_linear_fwd_h3d_img(_p(mem), _p(planes), _p(bias), _p(y), _p(row_inv), M, N, K, _p(mem_amax), _p(sec_amax),
                                                rows // 2, _stream()), "ttts_linear_fwd_h3d_img (stacked K/V)")
         ctx.save_for_backward(mem)
@@ -1351,8 +1346,7 @@ class CrossKVProjFn(torch.autograd.Function):
         dmem = None
         if ctx.needs_input_grad[0]:
             dmem = torch.empty_like(mem)
-            _lib.check(lib.ttts_linear_bwd_data_h3(_p(dy), _p(_stacked_planes(ctx.owner, ws, 5)), None, _p(dmem), M, N, K, None, 1.0,
-                                                   _p(am), None, _stream()), "ttts_linear_bwd_data_h3 (stacked K/V)")
+            _linear_bwd_data(dy, None, dmem, M, N, K, am, w_image=_stacked_planes(ctx.owner, ws, H3_LIN_BWD))
         out_w = [None] * L
         out_b = [None] * L
         if any(ctx.needs_input_grad[6:6 + L]):
@@ -1377,7 +1371,7 @@ class CrossKVProjFn(torch.autograd.Function):
 
 def cross_kv_ok(mem: torch.Tensor, attns, n_head: int) -> bool:
     """can the K/V projections of `attns` (the decoder layers' MultiheadAttention modules) run as one head-image GEMM?"""
-    if not (FUSED_CROSS_KV and HEAD_IMAGES and len(attns) > 1 and mem.is_cuda and WGRAD_MODE == "h3" and BWD_MODE == "h3"):
+    if not (FUSED_CROSS_KV and HEAD_IMAGES and len(attns) > 1 and mem.is_cuda):
         return False
     w0 = attns[0].in_proj_weight
     d = w0.shape[1]
@@ -1403,23 +1397,6 @@ def cross_kv_projection(mem: torch.Tensor, attns, owner):
 
 
 # ----------------------------------------------------------------------------------------------- heads
-def _mel_head(lib, x, w_mel, b_mel, mel, M, N, K, x_amax, mel_amax):
-    """mel = x w_mel^T + b_mel into the given buffer, in the configured form; -> the partial maxima of x it used (or None)"""
-    if _fwd_h3(K, N):
-        if x_amax is None:
-            x_amax = _amax(x)
-        _lib.check(lib.ttts_linear_fwd_h3(_p(x), _p(_planes(w_mel, 4, N, K)), _p(b_mel), None, _p(mel), M, N, K,
-                                          ACT_NONE, 0.0, 0, None, 0, 0, _p(x_amax), _p(mel_amax), _stream()),
-                   "ttts_linear_fwd_h3")
-    elif GEMM_MODE == "x6":
-        _lib.check(lib.ttts_linear_fwd_x6(_p(x), _p(_planes(w_mel, 0, N, K)), _p(b_mel), None, _p(mel), M, N, K,
-                                          ACT_NONE, 0.0, 0, None, 0, 0, _stream()), "ttts_linear_fwd_x6")
-    else:
-        _lib.check(lib.ttts_linear_fwd(_p(x), _p(w_mel), _p(b_mel), None, _p(mel), M, N, K, ACT_NONE, 0.0,
-                                       0, None, 0, 0, _stream()), "ttts_linear_fwd")
-    return x_amax
-
-
 class PostnetTwin:
     """The mel predictions of BOTH forwards of a training step as one twin batch (see `_twin`): the no-grad forward, which runs
     first, leaves its prediction in the SECOND half of `full` (2 B, T, n_mels) and does not run the post-net; the grad forward
@@ -1449,7 +1426,7 @@ class HeadsFn(torch.autograd.Function):
         mel = box.full[:x.shape[0]] if box is not None else torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
         stop = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
         w_mel = _chk(w_mel, "w_mel")
-        x_amax = _mel_head(lib, x, w_mel, b_mel, mel, M, N, K, x_amax, mel_amax)
+        x_amax = _linear_fwd(x, w_mel, b_mel, None, mel, M, N, K, x_amax, mel_amax, tiles=False)
         _lib.check(lib.ttts_rowdot_fwd(_p(x), _p(_chk(w_stop, "w_stop")), _p(b_stop), _p(stop), M, K, _stream()),
                    "ttts_rowdot_fwd")
         ctx.save_for_backward(x, w_mel, w_stop)
@@ -1466,19 +1443,7 @@ class HeadsFn(torch.autograd.Function):
         dmel = _chk(dmel, "heads.dmel")
         dstop = _chk(dstop, "heads.dstop")
         dx = torch.empty_like(x)
-        dmel_am = None
-        if _bwd_h3(N, K):
-            dmel_am = _amax(dmel)                  # (shared with the weight gradient below)
-            _lib.check(lib.ttts_linear_bwd_data_h3(_p(dmel), _p(_planes(w_mel, 5, K, N)), None, _p(dx), M, N, K, None, 1.0,
-                                                   _p(dmel_am), None, _stream()), "ttts_linear_bwd_data_h3")
-        elif GEMM_MODE == "x6":
-            _lib.check(lib.ttts_linear_bwd_data_x6(_p(dmel), _p(_planes(w_mel, 1, K, N)), None, _p(dx), M, N, K, None, 1.0,
-                                                   _stream()),
-                       "ttts_linear_bwd_data_x6")
-        else:
-            _lib.check(lib.ttts_linear_bwd_data(_p(dmel), _p(w_mel), None, _p(dx), M, N, K, None, 1.0, _stream()),
-                       "ttts_linear_bwd_data")
-        ws = _ws(lib.ttts_wgrad_workspace_bytes(M, N, K, 1), x.device)
+        dmel_am = _linear_bwd_data(dmel, w_mel, dx, M, N, K, None, tiles=False)      # (the maxima: shared with the weight gradient)
         sk, acc, queue = ctx.sinks
         ws2 = _ws(lib.ttts_rowdot_bwd_workspace_bytes(K), x.device)
         if sk is not None:
@@ -1489,14 +1454,7 @@ class HeadsFn(torch.autograd.Function):
             t_bm = db_mel = torch.empty(N, dtype=torch.float32, device=x.device)
             t_ws = dw_stop = torch.empty_like(w_stop)
             t_bs = db_stop = torch.empty(1, dtype=torch.float32, device=x.device)
-        cls = lib.ttts_wgrad_group_ok(M, N, K, 1) if (WGRAD_GROUPS and DEFER_REDUCE and sk is not None and queue is not None and
-                                                       WGRAD_MODE == "h3" and _wgrad_is_split(N, K)) else 0
-        if cls:
-            queue.defer_wgrad(cls, dmel, dmel_am if dmel_am is not None else _amax(dmel), x,
-                              ctx.x_amax if ctx.x_amax is not None else _amax(x), t_wm, t_bm, M, N, K)
-        else:
-            _lib.check(_wgrad(lib, "ttts_linear_bwd_weight", dmel, dmel_am, x, ctx.x_amax, _wgrad_is_split(N, K), _qarg(queue, ws),
-                              _p(t_wm), _p(t_bm), _p(ws), ws.numel() * 4, M, N, K, 0, 0, acc), "ttts_linear_bwd_weight")
+        _weight_grad(dmel, dmel_am, x, ctx.x_amax, t_wm, t_bm, acc, queue, M, N, K)
         _lib.check(lib.ttts_rowdot_bwd(_p(dstop), _p(x), _p(w_stop), _p(dx), _p(t_ws), _p(t_bs), _p(ws2),
                                        ws2.numel() * 4, M, K, acc, _qarg(queue, ws2), _stream()), "ttts_rowdot_bwd")
         return dx, dw_mel, db_mel, dw_stop, db_stop, None, None, None
@@ -1513,18 +1471,17 @@ def heads(x, w_mel, b_mel, w_stop, b_stop, need_stop: bool = True, box: Optional
         # the no-grad forward of a twin post-net: the prediction goes behind the place of the grad forward's
         if torch.is_grad_enabled() or need_stop or x.dim() != 3:
             raise ValueError("heads(box=<empty PostnetTwin>) is the no-grad forward's call (need_stop=False, (B, T, d) input)")
-        lib = _lib.load()
         x = _chk(x, "heads.x")
         B = x.shape[0]
         box.full = torch.empty(2 * B, x.shape[1], N, dtype=torch.float32, device=x.device)
-        box.amax = _amax_slots(x.device, True) if _fwd_h3(K, N) else None
-        _mel_head(lib, x, _chk(w_mel, "w_mel"), b_mel, box.full[B:], x.numel() // K, N, K, None, box.amax)
+        box.amax = _amax_slots(x.device, True) if _h3_shape_ok(K, N) else None
+        _linear_fwd(x, _chk(w_mel, "w_mel"), b_mel, None, box.full[B:], x.numel() // K, N, K, None, box.amax, tiles=False)
         return box.full[B:], None
     if not need_stop:
         if torch.is_grad_enabled() and (x.requires_grad or w_stop.requires_grad):
             raise ValueError("heads(need_stop=False) is for no-grad forwards: the stop head's gradients would be lost")
         return linear(x, w_mel, b_mel, publish_amax=True), None
-    h3 = x.is_cuda and _fwd_h3(K, N)
+    h3 = x.is_cuda and _h3_shape_ok(K, N)
     x_am = _amax(x) if h3 else None
     if box is not None:
         if box.full.shape != (2 * x.shape[0], x.shape[1], N) or box.full.device != x.device:
@@ -1561,7 +1518,7 @@ class ConvBNFn(torch.autograd.Function):
         y = torch.empty(B, T, cout, dtype=torch.float32, device=dev)
         M = B * T
         bn_nblk, bn_ws = 0, None
-        if _fwd_h3(taps * cin, cout, cin):
+        if _h3_shape_ok(taps * cin, cout, cin):
             if x_amax is None:
                 x_amax = _amax(x)
             if training and M > 1:
@@ -1569,17 +1526,11 @@ class ConvBNFn(torch.autograd.Function):
                 bn_nblk = lib.ttts_conv1d_fwd_h3_bn_blocks(B, T, cin, cout, taps)
                 if bn_nblk > 0:
                     bn_ws = _ws(lib.ttts_bn_workspace_bytes(M, cout), dev)
-            _lib.check(lib.ttts_conv1d_fwd_h3(_p(x), _p(_planes(conv_w, 6, cout, taps * cin, cin, taps)), _p(conv_b), _p(y),
+            _lib.check(lib.ttts_conv1d_fwd_h3(_p(x), _p(_planes(conv_w, H3_CONV_FWD, cout, taps * cin, cin, taps)), _p(conv_b), _p(y),
                                               B, T, cin, cout, taps, _p(x_amax), _p(bn_ws), _stream()), "ttts_conv1d_fwd_h3")
-        elif GEMM_MODE == "x6":
-            _lib.check(lib.ttts_conv1d_fwd_x6(_p(x), _p(_planes(conv_w, 2, cout, taps * cin, cin, taps)), _p(conv_b), _p(y),
+        else:                                   # the shape fallback (see _linear_fwd): channels no multiple of 4
+            _lib.check(lib.ttts_conv1d_fwd_x6(_p(x), _p(_planes(conv_w, X6_CONV_FWD, cout, taps * cin, cin, taps)), _p(conv_b), _p(y),
                                               B, T, cin, cout, taps, _stream()), "ttts_conv1d_fwd_x6")
-        else:
-            w_fwd = torch.empty(cout * taps * cin, dtype=torch.float32, device=dev)
-            _lib.check(lib.ttts_conv1d_pack_weight(_p(conv_w), _p(w_fwd), None, cout, cin, taps, _stream()),
-                       "ttts_conv1d_pack_weight")
-            _lib.check(lib.ttts_conv1d_fwd(_p(x), _p(w_fwd), _p(conv_b), _p(y), B, T, cin, cout, taps, _stream()),
-                       "ttts_conv1d_fwd")
         mean = torch.empty(cout, dtype=torch.float32, device=dev)
         invstd = torch.empty(cout, dtype=torch.float32, device=dev)
         if training and bn_ws is not None:
@@ -1614,7 +1565,7 @@ class ConvBNFn(torch.autograd.Function):
         B, T, cin = x.shape
         cout, _, taps = conv_w.shape
         dev = x.device
-        if not _fwd_h3(taps * cin, cout, cin):
+        if not _h3_shape_ok(taps * cin, cout, cin):
             raise ValueError("conv_bn: a twin batch runs on the fp16x3 form only")
         Bk, M = 2 * B, B * T
         y_k = torch.empty(Bk, T, cout, dtype=torch.float32, device=dev)
@@ -1634,7 +1585,7 @@ class ConvBNFn(torch.autograd.Function):
                     runs = {0: (0, s_, 0, 0), 1: (s_, nblk - s_, 0, 0)}
                 else:
                     runs = {0: (0, s_, s_ * chunk, cut), 1: (s_ + 1, nblk - s_ - 1, M, min((s_ + 1) * chunk, 2 * M) - M)}
-        _lib.check(lib.ttts_conv1d_fwd_h3(_p(x), _p(_planes(conv_w, 6, cout, taps * cin, cin, taps)), _p(conv_b), _p(y_k),
+        _lib.check(lib.ttts_conv1d_fwd_h3(_p(x), _p(_planes(conv_w, H3_CONV_FWD, cout, taps * cin, cin, taps)), _p(conv_b), _p(y_k),
                                           Bk, T, cin, cout, taps, _p(x_amax), _p(bn_ws), _stream()), "ttts_conv1d_fwd_h3")
         mi = torch.empty(2, 2, cout, dtype=torch.float32, device=dev)          # [half][mean, invstd]
         halves = (1, 0)                           # the no-grad forward's half first
@@ -1692,8 +1643,7 @@ class ConvBNFn(torch.autograd.Function):
             t_be = dbeta = torch.empty_like(beta)
         ws = _ws(lib.ttts_bn_workspace_bytes(M, cout), dev)
         # the BatchNorm backward writes dy, the gradient both conv GEMMs below consume: it leaves dy's partial maxima too
-        want_am = (ctx.needs_input_grad[0] and _bwd_h3(taps * cout, cin, cout)) or \
-                  (WGRAD_MODE == "h3" and _wgrad_is_split(cout, cin))
+        want_am = (ctx.needs_input_grad[0] and _h3_shape_ok(taps * cout, cin, cout)) or _wgrad_is_split(cout, cin)
         am = _amax_slots(dev, True) if want_am else None
         _lib.check(lib.ttts_bn_bwd(_p(dz), _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dy), _p(t_g), _p(t_be),
                                    _p(ws), ws.numel() * 4, M, cout, act, drop_p, seed, ctx.ss, acc, _p(am), 1 if training else 0,
@@ -1701,28 +1651,13 @@ class ConvBNFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            if _bwd_h3(taps * cout, cin, cout):
-                _lib.check(lib.ttts_conv1d_bwd_data_h3(_p(dy), _p(_planes(conv_w, 7, cin, taps * cout, cout, taps)), _p(dx),
+            if _h3_shape_ok(taps * cout, cin, cout):
+                _lib.check(lib.ttts_conv1d_bwd_data_h3(_p(dy), _p(_planes(conv_w, H3_CONV_BWD, cin, taps * cout, cout, taps)), _p(dx),
                                                        B, T, cin, cout, taps, _p(am), _stream()), "ttts_conv1d_bwd_data_h3")
-            elif GEMM_MODE == "x6":
-                _lib.check(lib.ttts_conv1d_bwd_data_x6(_p(dy), _p(_planes(conv_w, 3, cin, taps * cout, cout, taps)), _p(dx),
+            else:                               # the shape fallback
+                _lib.check(lib.ttts_conv1d_bwd_data_x6(_p(dy), _p(_planes(conv_w, X6_CONV_BWD, cin, taps * cout, cout, taps)), _p(dx),
                                                        B, T, cin, cout, taps, _stream()), "ttts_conv1d_bwd_data_x6")
-            else:
-                w_bwd = torch.empty(cin * taps * cout, dtype=torch.float32, device=dev)
-                _lib.check(lib.ttts_conv1d_pack_weight(_p(conv_w), None, _p(w_bwd), cout, cin, taps, _stream()),
-                           "ttts_conv1d_pack_weight")
-                _lib.check(lib.ttts_conv1d_bwd_data(_p(dy), _p(w_bwd), _p(dx), B, T, cin, cout, taps, _stream()),
-                           "ttts_conv1d_bwd_data")
-        cls = lib.ttts_wgrad_group_ok(M, cout, cin, taps) if (WGRAD_GROUPS and DEFER_REDUCE and sk is not None and queue is not None and
-                                                              WGRAD_MODE == "h3" and _wgrad_is_split(cout, cin)) else 0
-        if cls:       # a gradient sink: nobody reads the result before the optimizer, so it waits for its group
-            queue.defer_wgrad(cls, dy, am if am is not None else _amax(dy), x, ctx.x_amax if ctx.x_amax is not None else _amax(x),
-                              t_w, t_b, M, cout, cin, taps, T)
-        else:
-            ws2 = _ws(lib.ttts_wgrad_workspace_bytes(M, cout, cin, taps), dev)
-            _lib.check(_wgrad(lib, "ttts_conv1d_bwd_weight", dy, am, x, ctx.x_amax, _wgrad_is_split(cout, cin),
-                              _qarg(queue, ws2) if sk is not None else None, _p(t_w), _p(t_b), _p(ws2), ws2.numel() * 4, B, T, cin,
-                              cout, taps, acc), "ttts_conv1d_bwd_weight")
+        _weight_grad(dy, am, x, ctx.x_amax, t_w, t_b, acc, queue, M, cout, cin, taps, T, conv=True)
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1736,7 +1671,7 @@ def conv_bn(x, conv_w, conv_b, gamma, beta, running_mean, running_var, nbt, trai
     x_full = _twin(x)
     twin = [x_full, [], bool(twin_last)] if x_full is not None else None
     x_am = None
-    if x.is_cuda and _fwd_h3(taps * cin, cout, cin):
+    if x.is_cuda and _h3_shape_ok(taps * cin, cout, cin):
         x_am = _amax(x) if (getattr(x, "_ttts_amax", None) is not None or x_full is None) else _amax(x_full)
     z_am = _amax_slots(x.device, True) if (publish_amax and x.is_cuda) else None
     z = ConvBNFn.apply(x, conv_w, conv_b, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, act,
@@ -1840,30 +1775,20 @@ def layer_norm(x, gamma, beta, eps=1e-5, sole_consumer=False, publish_amax=True,
 # ----------------------------------------------------------------------------------------------- attention
 def _attn_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_am=None, k_am=None,
               v_am=None, o_am=None, q_scale: float = 0.125):
-    """q_am / k_am / v_am: partial maxima of the operands (fp16x3 form; required there); o_am: None, or a zeroed
-    AMAX_SLOTS-slot array that receives max|o|."""
+    """q_am / k_am / v_am: partial maxima of the operands (required); o_am: None, or a zeroed AMAX_SLOTS-slot array that
+    receives max|o|.  -> (o, stat, attn); stat[0] = lse (natural units), stat[1:] = the row statistics the backward reads."""
     lib = _lib.load()
     dev = lens.device
     o = torch.empty(B, Tq, H * 64, dtype=torch.float32, device=dev)
-    # lse (natural units) and, in the fp16x3 form, the row statistics in the kernel's own units behind it: rows 1-3 of `stat`
-    stat = torch.empty(4 if ATTN_FWD_MODE == "h3" else 1, B, H, Tq, dtype=torch.float32, device=dev)
-    lse = stat[0]
+    if q_am is None or k_am is None or v_am is None:
+        raise ValueError("attention: the partial maxima of q, k and v are required")
+    # lse (natural units) and the row statistics in the kernel's own units behind it: rows 1-3 of `stat`
+    stat = torch.empty(4, B, H, Tq, dtype=torch.float32, device=dev)
     attn = torch.empty(B, H, Tq, Tk, dtype=torch.float32, device=dev) if need_weights else None
-    args = (q, k, v, _p(o), _p(lse), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv, H * 64, 1 if causal else 0,
-            float(q_scale), float(drop_p), seed, _ss())
-    if ATTN_FWD_MODE == "h3":
-        if q_am is None or k_am is None or v_am is None:
-            raise ValueError("attention (fp16x3 form): the partial maxima of q, k and v are required")
-        _lib.check(lib.ttts_attention_fwd_h3(*args, _p(q_am), _p(k_am), _p(v_am), _p(o_am), _p(stat[1:]), _stream()),
-                   "ttts_attention_fwd_h3")
-    else:
-        fwd = lib.ttts_attention_fwd_x6 if ATTN_FWD_MODE == "x6" else lib.ttts_attention_fwd
-        _lib.check(fwd(*args, _stream()), "ttts_attention_fwd")
+    _lib.check(lib.ttts_attention_fwd_h3(q, k, v, _p(o), _p(stat[0]), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv, H * 64,
+                                         1 if causal else 0, float(q_scale), float(drop_p), seed, _ss(), _p(q_am), _p(k_am),
+                                         _p(v_am), _p(o_am), _p(stat[1:]), _stream()), "ttts_attention_fwd_h3")
     return o, stat, attn
-
-
-def _attn_h3() -> bool:
-    return ATTN_FWD_MODE == "h3" or ATTN_BWD_MODE == "h3"
 
 
 def _off(t: torch.Tensor, col: int):
@@ -2117,7 +2042,7 @@ class SelfAttentionFn(torch.autograd.Function):
         B, T, d3 = qkv.shape
         d = d3 // 3
         hd = _head_dim(d, n_head)
-        if qkv_amax is None and _attn_h3():
+        if qkv_amax is None:
             qkv_amax = _amax(qkv)
         pads = None
         if hd == 64:
@@ -2142,14 +2067,14 @@ class SelfAttentionFn(torch.autograd.Function):
     def backward(ctx, do):
         lib = _lib.load()
         qkv, o64, stat, lens, *pads = ctx.saved_tensors
-        lse, rowstat = stat[0], (stat[1:] if stat.shape[0] == 4 else None)
+        lse, rowstat = stat[0], stat[1:]
         n_head, causal, drop_p, seed, hd = ctx.cfg
         B, T, d3 = qkv.shape
         d = d3 // 3
         do = _chk(do, "self_attention.do")
         dqkv = torch.empty_like(qkv)
         delta = torch.empty(lse.shape, dtype=torch.float32, device=lse.device)
-        am = _amax_slots(qkv.device, True) if ATTN_BWD_MODE == "h3" else None     # max|dqkv| for the in-projection gradients
+        am = _amax_slots(qkv.device, True)                                     # max|dqkv| for the in-projection gradients
         qa = ctx.qkv_amax
         if hd == 64:
             ins, ld, do64 = (_off(qkv, 0), _off(qkv, d), _off(qkv, 2 * d)), d3, do
@@ -2161,12 +2086,11 @@ class SelfAttentionFn(torch.autograd.Function):
             outs, ldg = tuple(_p(t) for t in grads), n_head * 64
         _lib.check(_attn_bwd(lib, do64, am, am, qa, qa, qa, rowstat, *ins, _p(o64), _p(do64), _p(lse), _p(delta), *outs, _p(lens),
                              B, n_head, T, T, ld, ld, ld, n_head * 64, ldg, ldg, ldg, 1 if causal else 0, hd ** -0.5, drop_p,
-                             seed, ctx.ss), "ttts_attention_bwd")
+                             seed, ctx.ss), "ttts_attention_bwd_h3")
         if hd != 64:
             for g, c in zip(grads, (0, d, 2 * d)):
                 _unpad_heads(g, dqkv, c, d3, B * T, n_head, hd)
-        if am is not None:
-            dqkv._ttts_amax = am
+        dqkv._ttts_amax = am
         return dqkv, None, None, None, None, None, None, None
 
 
@@ -2181,9 +2105,8 @@ class CrossAttentionFn(torch.autograd.Function):
         B, Tq, d = q.shape
         Tk = kv.shape[1]
         hd = _head_dim(d, n_head)
-        if _attn_h3():
-            q_amax = _amax(q) if q_amax is None else q_amax
-            kv_amax = _amax(kv) if kv_amax is None else kv_amax
+        q_amax = _amax(q) if q_amax is None else q_amax
+        kv_amax = _amax(kv) if kv_amax is None else kv_amax
         pads = None
         if hd == 64:
             ptrs, lds = (_off(q, 0), _off(kv, 0), _off(kv, d)), (d, 2 * d, 2 * d)
@@ -2214,7 +2137,7 @@ class CrossAttentionFn(torch.autograd.Function):
             return None, None, None, None, None, None, None, None, None, None
         lib = _lib.load()
         q, kv, o64, stat, lens, *pads = ctx.saved_tensors
-        lse, rowstat = stat[0], (stat[1:] if stat.shape[0] == 4 else None)
+        lse, rowstat = stat[0], stat[1:]
         n_head, drop_p, seed, hd = ctx.cfg
         B, Tq, d = q.shape
         Tk = kv.shape[1]
@@ -2222,9 +2145,7 @@ class CrossAttentionFn(torch.autograd.Function):
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         delta = torch.empty(lse.shape, dtype=torch.float32, device=lse.device)
-        am_q = am_kv = None
-        if ATTN_BWD_MODE == "h3":
-            am_q, am_kv = _amax_slots(q.device, True), _amax_slots(q.device, True)
+        am_q, am_kv = _amax_slots(q.device, True), _amax_slots(q.device, True)
         qa, kva = ctx.amax
         if hd == 64:
             ins, lds, do64 = (_off(q, 0), _off(kv, 0), _off(kv, d)), (d, 2 * d, 2 * d), do
@@ -2238,13 +2159,12 @@ class CrossAttentionFn(torch.autograd.Function):
             outs, ldg = tuple(_p(t) for t in grads), (n_head * 64,) * 3
         _lib.check(_attn_bwd(lib, do64, am_q, am_kv, qa, kva, kva, rowstat, *ins, _p(o64), _p(do64), _p(lse), _p(delta), *outs,
                              _p(lens), B, n_head, Tq, Tk, *lds, n_head * 64, *ldg, 0, hd ** -0.5, drop_p, seed, ctx.ss),
-                   "ttts_attention_bwd")
+                   "ttts_attention_bwd_h3")
         if hd != 64:
             _unpad_heads(grads[0], dq, 0, d, B * Tq, n_head, hd)
             _unpad_heads(grads[1], dkv, 0, 2 * d, B * Tk, n_head, hd)
             _unpad_heads(grads[2], dkv, d, 2 * d, B * Tk, n_head, hd)
-        if am_q is not None:
-            dq._ttts_amax, dkv._ttts_amax = am_q, am_kv
+        dq._ttts_amax, dkv._ttts_amax = am_q, am_kv
         return dq, dkv, None, None, None, None, None, None, None, None
 
 
@@ -2268,9 +2188,8 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
         return o
     if _twin(qkv) is not None:
         raise ValueError("self_attention: a twin batch runs on head images only")
-    h3 = qkv.is_cuda and _attn_h3()
-    am = _amax(qkv) if h3 else None
-    o_am = _amax_slots(qkv.device, True) if (qkv.is_cuda and ATTN_FWD_MODE == "h3") else None
+    am = _amax(qkv) if qkv.is_cuda else None
+    o_am = _amax_slots(qkv.device, True) if qkv.is_cuda else None
     o = SelfAttentionFn.apply(qkv, lens, n_head, causal, drop_p, seed, am, o_am)
     if o_am is not None:
         o._ttts_amax = o_am
@@ -2292,9 +2211,8 @@ def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_wei
         o, attn = CrossAttentionImgFn.apply(q.cells, q, kv.cells, kv, lens, n_head, drop_p, seed, need_weights, o_am)
         o._ttts_amax = o_am
         return o, attn
-    h3 = q.is_cuda and _attn_h3()
-    q_am, kv_am = (_amax(q), _amax(kv)) if h3 else (None, None)
-    o_am = _amax_slots(q.device, True) if (q.is_cuda and ATTN_FWD_MODE == "h3") else None
+    q_am, kv_am = (_amax(q), _amax(kv)) if q.is_cuda else (None, None)
+    o_am = _amax_slots(q.device, True) if q.is_cuda else None
     o, attn = CrossAttentionFn.apply(q, kv, lens, n_head, drop_p, seed, need_weights, q_am, kv_am, o_am)
     if o_am is not None:
         o._ttts_amax = o_am
