@@ -227,7 +227,7 @@ def test_self_attention(B, H, T, causal, lens):
     ref = o.transpose(1, 2).reshape(B, T, d)
     ref.backward(do.double())
     qg = _g(qkv)
-    out = ops.SelfAttentionFn.apply(qg, lens_t.to(_dev()), H, causal, 0.0, 0)
+    out, _ = ops.AttentionFn.apply(qg, None, lens_t.to(_dev()), H, causal, 0.0, 0, False)
     out.backward(do.to(_dev()))
     assert rel_l2(out, ref) < TOL
     assert rel_l2(qg.grad, qd.grad) < TOL
@@ -247,7 +247,7 @@ def test_cross_attention(B, H, Tq, Tk, lens):
     ref = o.transpose(1, 2).reshape(B, Tq, d)
     ref.backward(do.double())
     qg, kvg = _g(q_), _g(kv_)
-    out, attn = ops.CrossAttentionFn.apply(qg, kvg, lens_t.to(_dev()), H, 0.0, 0)
+    out, attn = ops.AttentionFn.apply(qg, kvg, lens_t.to(_dev()), H, False, 0.0, 0, True)
     out.backward(do.to(_dev()))
     assert rel_l2(out, ref) < TOL
     assert rel_l2(attn, a) < TOL
@@ -258,7 +258,7 @@ def test_cross_attention(B, H, Tq, Tk, lens):
     assert rel_l2(kvg.grad, kvd.grad) < TOL
     # the same attention without the weights output (single-pass online softmax path)
     q2, kv2 = _g(q_), _g(kv_)
-    out2, none_w = ops.CrossAttentionFn.apply(q2, kv2, lens_t.to(_dev()), H, 0.0, 0, False)
+    out2, none_w = ops.AttentionFn.apply(q2, kv2, lens_t.to(_dev()), H, False, 0.0, 0, False)
     out2.backward(do.to(_dev()))
     assert none_w.numel() == 0
     assert rel_l2(out2, ref) < TOL and rel_l2(q2.grad, qd.grad) < TOL and rel_l2(kv2.grad, kvd.grad) < TOL
@@ -316,7 +316,7 @@ def test_attention_on_random_shapes():
 @pytest.mark.parametrize("hd", [128, 192])
 def test_attention_with_heads_wider_than_64(hd):
     """head_dim > 64 (the reference takes any nhead: /root/reference/model/model.py:139-161): ops.self_attention /
-    cross_attention run as tensor algebra on library GEMMs (ops._attention_wide_heads) with the conventions of the kernels --
+    cross_attention run as tensor algebra on library GEMMs (ops.masked_attention) with the conventions of the kernels --
     ragged key lengths, causal mask, weights returned, an utterance without keys gives zeros -- forward, weights and every
     gradient against fp64; with dropout the weights are the dropped ones (as the kernels return them)."""
     from transformertts_amd import ops
@@ -454,8 +454,8 @@ def test_dropout_masks_are_consistent_and_calibrated():
     q_, kv_ = _rand(B, Tq, 128, seed=4), _rand(B, Tk, 256, seed=5)
     lens = torch.full((B,), Tk, dtype=torch.int64, device=dev)
     qg, kvg = _g(q_), _g(kv_)
-    _, a0 = ops.CrossAttentionFn.apply(qg, kvg, lens, H, 0.0, 0)
-    o1, a1 = ops.CrossAttentionFn.apply(qg, kvg, lens, H, 0.1, 77)
+    _, a0 = ops.AttentionFn.apply(qg, kvg, lens, H, False, 0.0, 0, True)
+    o1, a1 = ops.AttentionFn.apply(qg, kvg, lens, H, False, 0.1, 77, True)
     z = (a1 == 0).float().mean().item()
     assert abs(z - 0.1) < 0.01
     keep = a1 != 0

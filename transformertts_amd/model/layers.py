@@ -103,7 +103,7 @@ def _lens_and_kpm(lens: Optional[Tensor], kpm: Optional[Tensor], B: int, T: int,
 
 class MultiheadAttention(nn.Module):
     """Parameter layout of nn.MultiheadAttention (packed in-proj, `out_proj` sub-module).  Heads of 64 columns run on the
-    head-image kernels, narrower ones on the padded fp32 kernels, wider ones as tensor algebra (ops._attention_wide_heads)."""
+    head-image kernels, narrower ones on the padded fp32 kernels, wider ones as tensor algebra (ops.masked_attention)."""
 
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0):
         super().__init__()
@@ -120,27 +120,32 @@ class MultiheadAttention(nn.Module):
     def _p(self) -> float:
         return self.dropout if self.training else 0.0
 
+    def _out(self, ctx: Tensor, residual: Tensor, out_drop: float, skip, from_kernel: bool) -> Tensor:
+        """residual + drop(out_proj(ctx)); `from_kernel`: ctx left an attention kernel and nothing but this GEMM reads it (see
+        LinearFn.forward)"""
+        if from_kernel:
+            ctx._ttts_sole_consumer = True
+        return ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual, drop_p=out_drop,
+                          seed=ops.seeds.next() if out_drop > 0 else 0, skip_out=skip)
+
     def self_attention(self, x: Tensor, lens: Tensor, causal: bool, residual: Tensor, out_drop: float,
                        dead: Optional[Tensor] = None, add_mask: Optional[Tensor] = None) -> Tensor:
         """residual + drop(out_proj(attention(in_proj(x)))); `dead` / `add_mask`: masks the kernels do not derive from lengths
         (`_resolve_kpm`, `_additive_mask`) -- that attention runs in `ops.masked_attention` between the same two GEMMs"""
         skip = ops.SkipToken() if residual is x else None      # the skip gradient rides in the in-projection's epilogue
-        if dead is not None or add_mask is not None:
-            d = self.embed_dim
-            qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias, skip_in=skip, publish_amax=True)
-            ctx, _ = ops.masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, self.num_heads, causal,
-                                          self._p(), dead, add_mask)
-            return ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual, drop_p=out_drop,
-                              seed=ops.seeds.next() if out_drop > 0 else 0, skip_out=skip)
+        masked = dead is not None or add_mask is not None
         # 64-column heads: q / k / v leave the in-projection as a head image (f16 hi / lo pieces with per-(row, head) scales in the
         # cells fp32 would occupy) and attention stages them by LDS-DMA; narrower heads take the fp32 path through padded copies
-        img = 3 if ops.head_image_ok(x, self.in_proj_weight, self.num_heads, 3) else 0
+        img = 3 if (not masked and ops.head_image_ok(x, self.in_proj_weight, self.num_heads, 3)) else 0
         qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias, skip_in=skip, publish_amax=not img, head_image_sections=img)
         p = self._p()
-        ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, ops.seeds.next() if p > 0 else 0)
-        ctx._ttts_sole_consumer = True      # only the out-projection below reads it (see LinearFn.forward)
-        return ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual, drop_p=out_drop,
-                          seed=ops.seeds.next() if out_drop > 0 else 0, skip_out=skip)
+        if masked:
+            d = self.embed_dim
+            ctx, _ = ops.masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, self.num_heads, causal, p,
+                                          dead, add_mask)
+        else:
+            ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, ops.seeds.next() if p > 0 else 0)
+        return self._out(ctx, residual, out_drop, skip, not masked)
 
     def cross_attention(self, x: Tensor, mem: Tensor, mem_lens: Tensor, residual: Tensor, out_drop: float,
                         need_weights: bool = True, dead: Optional[Tensor] = None, add_mask: Optional[Tensor] = None, kv=None):
@@ -148,37 +153,23 @@ class MultiheadAttention(nn.Module):
         (`ops.cross_kv_projection`, TransformerDecoder.forward): the layer then projects only its queries"""
         d = self.embed_dim
         skip = ops.SkipToken() if residual is x else None
+        masked = dead is not None or add_mask is not None
+        if kv is not None and masked:
+            raise ValueError("cross_attention: a pre-projected K/V image takes length masks only")
         wq, wkv = ops.param_rows(self.in_proj_weight, 0, d), ops.param_rows(self.in_proj_weight, d, 3 * d)
-        if kv is not None:
-            if dead is not None or add_mask is not None:
-                raise ValueError("cross_attention: a pre-projected K/V image takes length masks only")
-            q = ops.linear(x, wq, ops.param_rows(self.in_proj_bias, 0, d), skip_in=skip, head_image_sections=1)
-            p = self._p()
-            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, ops.seeds.next() if p > 0 else 0, need_weights)
-            ctx._ttts_sole_consumer = True
-            out = ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual, drop_p=out_drop,
-                             seed=ops.seeds.next() if out_drop > 0 else 0, skip_out=skip)
-            return out, (attn if need_weights else None)
-        if dead is not None or add_mask is not None:
-            q = ops.linear(x, wq, ops.param_rows(self.in_proj_bias, 0, d), skip_in=skip, publish_amax=True)
-            kv = ops.linear(mem, wkv, ops.param_rows(self.in_proj_bias, d, 3 * d), publish_amax=True)
-            ctx, attn = ops.masked_attention(q, kv[..., :d], kv[..., d:], mem_lens, self.num_heads, False, self._p(), dead, add_mask)
-            out = ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual, drop_p=out_drop,
-                             seed=ops.seeds.next() if out_drop > 0 else 0, skip_out=skip)
-            return out, (attn if need_weights else None)
-        img = ops.head_image_ok(x, wq, self.num_heads, 1) and ops.head_image_ok(mem, wkv, self.num_heads, 2)
+        img = kv is not None or (not masked and ops.head_image_ok(x, wq, self.num_heads, 1) and
+                                 ops.head_image_ok(mem, wkv, self.num_heads, 2))
         q = ops.linear(x, wq, ops.param_rows(self.in_proj_bias, 0, d), skip_in=skip, publish_amax=not img,
                        head_image_sections=1 if img else 0)
-        kv = ops.linear(mem, wkv, ops.param_rows(self.in_proj_bias, d, 3 * d), publish_amax=not img,
-                        head_image_sections=2 if img else 0)
+        if kv is None:
+            kv = ops.linear(mem, wkv, ops.param_rows(self.in_proj_bias, d, 3 * d), publish_amax=not img,
+                            head_image_sections=2 if img else 0)
         p = self._p()
-        ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, ops.seeds.next() if p > 0 else 0, need_weights)
-        ctx._ttts_sole_consumer = True
-        if not need_weights:
-            attn = None
-        out = ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual, drop_p=out_drop,
-                         seed=ops.seeds.next() if out_drop > 0 else 0, skip_out=skip)
-        return out, attn
+        if masked:
+            ctx, attn = ops.masked_attention(q, kv[..., :d], kv[..., d:], mem_lens, self.num_heads, False, p, dead, add_mask)
+        else:
+            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, ops.seeds.next() if p > 0 else 0, need_weights)
+        return self._out(ctx, residual, out_drop, skip, not masked), (attn if need_weights else None)
 
 
 def _ffn_block(layer, x: Tensor, out_dropout: nn.Dropout, residual: Optional[Tensor] = None) -> Tensor:

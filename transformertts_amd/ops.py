@@ -71,6 +71,30 @@ def twin_pair(full: torch.Tensor):
     return a, full[B:]
 
 
+class _Twin:
+    """One op's view of a twin batch: what its wrapper hands the autograd Function and gets back from it.
+      x      the (2 B, ...) buffer whose first half the op's input is
+      other  None, or the buffer of a second input that travels with it (`linear`: the residual; image self-attention: the lengths)
+      last   `conv_bn(..., twin_last=True)`: nobody reads the no-grad half of the output, which then is no twin batch
+      out    the (2 B, ...) output buffer; the Function sets it, `_twin_attach` hangs it on the first half autograd returned"""
+    __slots__ = ("x", "other", "last", "out")
+
+    def __init__(self, x, other=None, last: bool = False):
+        self.x, self.other, self.last, self.out = x, other, bool(last), None
+
+
+def _twin_of(t, other=None, last: bool = False) -> Optional[_Twin]:
+    """the handle of the twin batch whose first half `t` is, or None"""
+    full = _twin(t)
+    return None if full is None else _Twin(full, _twin(other), last)
+
+
+def _twin_attach(y, twin: Optional[_Twin]):
+    if twin is not None and not twin.last:
+        y._ttts_twin = twin.out
+    return y
+
+
 def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty((max(int(nbytes), 16) + 3) // 4, dtype=torch.float32, device=device)
 
@@ -922,13 +946,12 @@ class LinearFn(torch.autograd.Function):
         r_ = _chk(residual, "linear.residual") if residual is not None else None
         if twin is not None:
             # x (and the residual) are the first halves of 2 B-utterance buffers: the kernel runs on the buffers -- same pointers,
-            # twice the rows --, autograd gets the first half of the output (`twin`: [x buffer, residual buffer or None, out list])
+            # twice the rows --, autograd gets the first half of the output (`twin`: a `_Twin`, `other` the residual's buffer)
             if x_image is not None or row_shift != 0:
                 raise ValueError("linear: a twin batch takes plain fp32 operands without a row shift")
             M = 2 * M
-            y_full = torch.empty(2 * x.shape[0], *x.shape[1:-1], N, dtype=torch.float32, device=x.device)
-            y = y_full[:x.shape[0]]
-            twin[2].append(y_full)
+            twin.out = torch.empty(2 * x.shape[0], *x.shape[1:-1], N, dtype=torch.float32, device=x.device)
+            y = twin.out[:x.shape[0]]
         else:
             y = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
         if r_ is not None and r_.shape != y.shape:
@@ -1127,15 +1150,11 @@ def linear(x, w, b=None, residual=None, act=ACT_NONE, drop_p=0.0, seed=0, row_sh
     grad_on = torch.is_grad_enabled()
     N, K = w.shape
     h3 = x.is_cuda and _h3_shape_ok(K, N)
-    x_full = _twin(x)
-    twin = None
-    if x_full is not None:
-        r_full = _twin(residual)
-        if residual is not None and r_full is None:
-            raise ValueError("linear: the residual of a twin batch must be a twin batch too")
-        twin = [x_full, r_full, []]
+    twin = _twin_of(x, residual)
+    if twin is not None and residual is not None and twin.other is None:
+        raise ValueError("linear: the residual of a twin batch must be a twin batch too")
     # (a twin batch's maxima cover BOTH halves: its producer published them over the whole buffer)
-    x_am = (_amax(x) if getattr(x, "_ttts_amax", None) is not None or x_full is None else _amax(x_full)) if h3 else None
+    x_am = (_amax(x) if getattr(x, "_ttts_amax", None) is not None or twin is None else _amax(twin.x)) if h3 else None
     y_am = None
     if h3 and publish_amax is not False and publish_amax is not None:
         y_am = publish_amax if isinstance(publish_amax, torch.Tensor) else _amax_slots(x.device, True)
@@ -1166,8 +1185,7 @@ def linear(x, w, b=None, residual=None, act=ACT_NONE, drop_p=0.0, seed=0, row_sh
         x_img = None
     y = LinearFn.apply(x, w, b, residual, act, drop_p, seed, row_shift, T, tok_out, tok_in, skip_in, skip_out, tok_drop,
                        x_am, y_am, x_img, y_himg, twin)
-    if twin is not None:
-        y._ttts_twin = twin[2][0]
+    _twin_attach(y, twin)
     if y_himg is not None:
         return HeadImage(y, y_himg[0], y_himg[1], y_himg[2])
     if y_am is not None:
@@ -1571,7 +1589,7 @@ class ConvBNFn(torch.autograd.Function):
         y_k = torch.empty(Bk, T, cout, dtype=torch.float32, device=dev)
         z_k = torch.empty(Bk, T, cout, dtype=torch.float32, device=dev)
         if x_amax is None:
-            x_amax = _amax(twin[0])
+            x_amax = _amax(twin.x)
         bn_ws, runs = None, None
         if training and M > 1:
             nblk = lib.ttts_conv1d_fwd_h3_bn_blocks(Bk, T, cin, cout, taps)
@@ -1607,13 +1625,13 @@ class ConvBNFn(torch.autograd.Function):
             elif not training:
                 _lib.check(lib.ttts_bn_eval_stats(_p(running_mean), _p(running_var), _p(mean), _p(invstd), cout, float(eps),
                                                   _stream()), "ttts_bn_eval_stats")
-            if h == 1 and len(twin) > 2 and twin[2]:
+            if h == 1 and twin.last:
                 continue                      # the no-grad half of the LAST layer of a twin pass: its statistics were all anybody wanted
             # (each half is a launch of its own whose element indices start at zero: the no-grad half draws from another seed)
             seed_h = seed if (h == 0 or seed == 0) else ((seed * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF)
             _lib.check(lib.ttts_bn_apply_fwd(_p(y_h), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(z_h), M, cout, act,
                                              float(drop_p), seed_h, _ss(), _p(z_amax), _stream()), "ttts_bn_apply_fwd")
-        twin[1].append(z_k)
+        twin.out = z_k
         ctx.save_for_backward(x, conv_w, y_k[:B], mi[0, 0], mi[0, 1], gamma, beta)
         ctx.x_amax = x_amax
         ctx.cfg = (training, act, float(drop_p), seed, conv_b is not None)
@@ -1668,16 +1686,14 @@ def conv_bn(x, conv_w, conv_b, gamma, beta, running_mean, running_var, nbt, trai
     rows still enter the convolution and update the running statistics, but are not normalised, and the result is an ordinary
     tensor of B utterances."""
     cout, cin, taps = conv_w.shape
-    x_full = _twin(x)
-    twin = [x_full, [], bool(twin_last)] if x_full is not None else None
+    twin = _twin_of(x, last=twin_last)
     x_am = None
     if x.is_cuda and _h3_shape_ok(taps * cin, cout, cin):
-        x_am = _amax(x) if (getattr(x, "_ttts_amax", None) is not None or x_full is None) else _amax(x_full)
+        x_am = _amax(x) if (getattr(x, "_ttts_amax", None) is not None or twin is None) else _amax(twin.x)
     z_am = _amax_slots(x.device, True) if (publish_amax and x.is_cuda) else None
     z = ConvBNFn.apply(x, conv_w, conv_b, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, act,
                        drop_p, seed, x_am, z_am, twin)
-    if twin is not None and not twin_last:
-        z._ttts_twin = twin[1][0]
+    _twin_attach(z, twin)
     if z_am is not None:
         z._ttts_amax = z_am
     return z
@@ -1704,7 +1720,7 @@ class LayerNormFn(torch.autograd.Function):
                                           _p(y_amax), _p(yi), _p(yv), _stream()), "ttts_layernorm_fwd")
         y = y_k
         if twin is not None:
-            twin[1].append(y_k)
+            twin.out = y_k
             y, mean, rstd = y_k[:x.shape[0]], mean[:M], rstd[:M]
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.sinks = _sinks(gamma, beta)
@@ -1759,12 +1775,10 @@ def layer_norm(x, gamma, beta, eps=1e-5, sole_consumer=False, publish_amax=True,
     # else reads -- of the gradient that Linear's backward consumes
     if emit_image is None:
         emit_image = LAYERNORM_IMAGES
-    x_full = _twin(x)
-    twin = [x_full, []] if x_full is not None else None
+    twin = _twin_of(x)
     y_img = _new_image(M, d, x.device) if (emit_image and x.is_cuda and _image_rows_ok(M, d) and twin is None) else None
     y = LayerNormFn.apply(x, gamma, beta, eps, tok, y_am, y_img, bool(emit_image and sole_consumer and twin is None), twin)
-    if twin is not None:
-        y._ttts_twin = twin[1][0]
+    _twin_attach(y, twin)
     if y_am is not None:
         y._ttts_amax = y_am
     if y_img is not None:
@@ -1795,35 +1809,60 @@ def _off(t: torch.Tensor, col: int):
     return c_void_p(t.data_ptr() + 4 * col)
 
 
-def _head_dim(d: int, n_head: int) -> int:
-    """Columns per head; the kernels work on 64-column heads and narrower ones are zero-padded to 64 (`_pad_heads`); wider
-    heads do not reach them (`_attention_wide_heads`)."""
+def _img_operand(cells: torch.Tensor, himg: "HeadImage", col: int):
+    """What the image launchers take per operand: (cells pointer, row stride, inverse-scale pointer, rows per inverse-scale plane)
+    of the 64-column heads that start at column `col` of `cells`, the cells of `himg` as the Function holds them."""
+    return _off(cells, col), cells.stride(1), himg.inv_of(col), himg.row_inv.shape[1]
+
+
+def _attn_img_fwd(q, k, v, o, stat, attn, lens, B, H, Tq, Tk, causal, drop_p, seed, v_am, o_am) -> None:
+    """o = softmax(mask(q k^T / 8)) v on head images (csrc/attention_img.hip); q / k / v: `_img_operand` (k and v lie in one
+    image: one plane size).  B utterances -- all of `o` and `stat` ((6, B, H, Tq): lse, then the five row-statistic planes the
+    backward reads); attn: None, or the (B, H, Tq, Tk) weights to fill; o_am: None, or a zeroed array that receives max|o|."""
+    lib = _lib.load()
+    (qp, ldq, qi, q_rows), (kp, ldk, ki, k_rows), (vp, ldv, vi, _) = q, k, v
+    _lib.check(lib.ttts_attention_fwd_img(qp, kp, vp, qi, ki, vi, _p(o), _p(stat[0]), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk,
+                                          ldv, o.shape[-1], 1 if causal else 0, 0.125, float(drop_p), seed, _ss(), _p(v_am),
+                                          _p(o_am), _p(stat[1:]), q_rows, k_rows, stat.stride(0), _stream()),
+               "ttts_attention_fwd_img")
+
+
+def _attn_img_bwd(q, k, v, o, do, stat, delta, dq, dk, dv, lens, B, H, Tq, Tk, causal, drop_p, seed, ss, dq_am, dkv_am,
+                  partials=None, q_splits: int = 1) -> None:
+    """Backward of `_attn_img_fwd` over the first B utterances of what it ran on (the planes of `stat` and of the inverse scales
+    keep the forward's strides).  delta: (B, H, Tq) scratch; dq / dk / dv: (pointer, row stride) of the gradient windows;
+    dq_am / dkv_am: zeroed arrays that receive max|dq| / max|dk, dv|; partials: None, or the (q_splits, B, Tk, 2d) scratch of a
+    dK / dV pass whose query range is split (`_dkv_query_splits`)."""
+    lib = _lib.load()
+    (qp, ldq, qi, q_rows), (kp, ldk, ki, k_rows), (vp, ldv, vi, _) = q, k, v
+    _lib.check(lib.ttts_attention_bwd_img(qp, kp, vp, qi, ki, vi, _p(o), _p(do), _p(stat[1:]), _p(delta), dq[0], dk[0], dv[0],
+                                          _p(lens), B, H, Tq, Tk, ldq, ldk, ldv, o.shape[-1], dq[1], dk[1], dv[1],
+                                          1 if causal else 0, 0.125, drop_p, seed, ss, _p(_amax(do)), _p(dq_am), _p(dkv_am),
+                                          _p(partials), q_splits, q_rows, k_rows, stat.stride(0), _stream()),
+               "ttts_attention_bwd_img")
+
+
+def _head_width(d: int, n_head: int) -> int:
+    """Columns per head.  The kernels work on 64-column heads: narrower ones are zero-padded to 64 (`_pad_heads`), wider ones
+    do not reach them (`masked_attention`)."""
     if n_head <= 0 or d % n_head != 0:
         raise ValueError(f"attention: d_model {d} is not divisible by {n_head} heads")
-    hd = d // n_head
-    if hd > 64:
-        raise ValueError(f"attention kernels take head_dim <= 64 (d_model {d}, heads {n_head}: head_dim {hd})")
-    return hd
+    return d // n_head
 
 
-def _wide_heads(d: int, n_head: int) -> bool:
-    if n_head <= 0 or d % n_head != 0:
-        raise ValueError(f"attention: d_model {d} is not divisible by {n_head} heads")
-    return d // n_head > 64
-
-
-def _attention_wide_heads(q, k, v, lens, n_head: int, causal: bool, drop_p: float, dead=None, add_mask=None):
-    """Attention as plain tensor algebra on the library's fp32 GEMMs, for the two cases the hand-written kernels do not take:
+def masked_attention(q, k, v, lens, n_head: int, causal: bool, drop_p: float, dead=None, add_mask=None):
+    """(context, per-head weights): attention as plain tensor algebra on the library's fp32 GEMMs, for the two cases the
+    hand-written kernels do not take:
       * heads wider than 64 columns (the reference takes any `nhead`, model/model.py:139-161; no BASELINE configuration has them):
         the kernels hold a 64-column head per fragment set;
-      * masks that are not "keys past a length" / causal (`masked_attention`: a key-padding mask with holes, `memory_mask`, an
-        arbitrary `tgt_mask` / `mask` -- arguments of the reference's layers, model/layers.py:29-74, that its model never passes).
+      * masks that are not "keys past a length" / causal (a key-padding mask with holes, `memory_mask`, an arbitrary `tgt_mask` /
+        `mask` -- arguments of the reference's layers, model/layers.py:29-74, that its model never passes).
     Same conventions as the kernels (weights returned AFTER dropout, rows without an allowed key give zeros), differentiated by
     autograd.  `dead` (B, Tk) bool replaces the keys-past-`lens` mask; `add_mask` (broadcastable to (B, H, Tq, Tk), finite) is
     added to the scaled scores as torch adds a float `attn_mask`.  Correct, not tuned."""
     B, Tq, d = q.shape
     Tk = k.shape[1]
-    hd = d // n_head
+    hd = _head_width(d, n_head)
     qh = q.reshape(B, Tq, n_head, hd).transpose(1, 2)
     kh = k.reshape(B, Tk, n_head, hd).transpose(1, 2)
     vh = v.reshape(B, Tk, n_head, hd).transpose(1, 2)
@@ -1846,13 +1885,6 @@ def _attention_wide_heads(q, k, v, lens, n_head: int, causal: bool, drop_p: floa
     return o, p
 
 
-def masked_attention(q, k, v, lens, n_head: int, causal: bool, drop_p: float, dead=None, add_mask=None):
-    """(context, per-head weights) under masks the kernels do not derive from lengths: see `_attention_wide_heads`."""
-    if n_head <= 0 or q.shape[-1] % n_head != 0:
-        raise ValueError(f"attention: d_model {q.shape[-1]} is not divisible by {n_head} heads")
-    return _attention_wide_heads(q, k, v, lens, n_head, causal, drop_p, dead, add_mask)
-
-
 def _pad_heads(src: torch.Tensor, col0: int, ld: int, rows: int, H: int, hd: int) -> torch.Tensor:
     """(rows, H*64): the H heads of `src` (row stride ld floats, head h at column col0 + h*hd) zero-padded to 64 columns."""
     dst = torch.empty(rows, H * 64, dtype=torch.float32, device=src.device)
@@ -1866,55 +1898,47 @@ def _unpad_heads(src: torch.Tensor, dst: torch.Tensor, col0: int, ld: int, rows:
 
 class SelfAttentionImgFn(torch.autograd.Function):
     """o = softmax(mask(q k^T / 8)) v on a packed in-projection output that arrived as a HEAD IMAGE (`linear(...,
-    head_image_sections=3)`): K / V tiles are staged by LDS-DMA, no split arithmetic (csrc/attention_img.hip).
-    `twin` = [image buffer, lengths buffer, out list]: qkv / lens are the first halves of a twin batch (see `_twin`): the forward
-    runs on all 2 B utterances, the backward on the first B (the inverse scales' head planes and the row statistics' planes keep the
-    buffer's strides: q_inv_rows / k_inv_rows / stat_plane of the C ABI)."""
+    head_image_sections=3)`; `himg` carries its inverse scales and maxima): K / V tiles are staged by LDS-DMA, no split
+    arithmetic (csrc/attention_img.hip).
+    `twin` (a `_Twin`, `other` the lengths' buffer): qkv / lens are the first halves of a twin batch (see `_twin`): the forward
+    runs on all 2 B utterances, the backward on the first B.  The self form never splits the query range of dK / dV."""
 
     @staticmethod
-    def forward(ctx, qkv, row_inv, sec_amax, lens, n_head, causal, drop_p, seed, o_amax=None, twin=None):
-        lib = _lib.load()
+    def forward(ctx, qkv, himg, lens, n_head, causal, drop_p, seed, o_amax=None, twin=None):
         qkv = _chk(qkv, "self_attention.qkv")
         lens = _chk(lens, "self_attention.lens", torch.int64)
         B, T, d3 = qkv.shape
         Bk = 2 * B if twin is not None else B             # utterances the kernel sees
-        d, M = d3 // 3, Bk * T
-        if row_inv.shape[1] != M or (twin is not None and (twin[1] is None or twin[1].shape[0] != Bk)):
+        d = d3 // 3
+        if himg.row_inv.shape[1] != Bk * T or (twin is not None and (twin.other is None or twin.other.shape[0] != Bk)):
             raise ValueError("self_attention: inverse scales / lengths do not match the image")
         o_k = torch.empty(Bk, T, d, dtype=torch.float32, device=qkv.device)
         stat = torch.empty(6, Bk, n_head, T, dtype=torch.float32, device=qkv.device)     # lse, then the five row-statistic planes
-        HM = n_head * M
-        _lib.check(lib.ttts_attention_fwd_img(_off(qkv, 0), _off(qkv, d), _off(qkv, 2 * d), _off(row_inv, 0), _off(row_inv, HM),
-                                              _off(row_inv, 2 * HM), _p(o_k), _p(stat[0]), None, _p(lens), Bk, n_head, T, T, d3, d3, d3, d,
-                                              1 if causal else 0, 0.125, float(drop_p), seed, _ss(), _p(sec_amax[2]), _p(o_amax),
-                                              _p(stat[1:]), 0, 0, 0, _stream()), "ttts_attention_fwd_img")
+        _attn_img_fwd(*(_img_operand(qkv, himg, c) for c in (0, d, 2 * d)), o_k, stat, None, lens, Bk, n_head, T, T, causal,
+                      drop_p, seed, himg.amax_of(2 * d), o_amax)
         o = o_k[:B] if twin is not None else o_k
         if twin is not None:
-            twin[2].append(o_k)
-        ctx.save_for_backward(qkv, row_inv, o, stat, lens)
-        ctx.cfg = (n_head, causal, float(drop_p), seed, Bk)
+            twin.out = o_k
+        ctx.save_for_backward(qkv, o, stat, lens)
+        ctx.himg = himg
+        ctx.cfg = (n_head, causal, float(drop_p), seed)
         ctx.ss = _ss()
         return o
 
     @staticmethod
     def backward(ctx, do):
-        lib = _lib.load()
-        qkv, row_inv, o, stat, lens = ctx.saved_tensors
-        n_head, causal, drop_p, seed, Bk = ctx.cfg
+        qkv, o, stat, lens = ctx.saved_tensors
+        n_head, causal, drop_p, seed = ctx.cfg
         B, T, d3 = qkv.shape
-        d, Mk = d3 // 3, Bk * T
-        HM = n_head * Mk
+        d = d3 // 3
         do = _chk(do, "self_attention.do")
         dqkv = torch.empty_like(qkv)
         delta = torch.empty(B, n_head, T, dtype=torch.float32, device=qkv.device)
         am = _amax_slots(qkv.device, True)                                     # max|dqkv| for the in-projection gradients
-        _lib.check(lib.ttts_attention_bwd_img(_off(qkv, 0), _off(qkv, d), _off(qkv, 2 * d), _off(row_inv, 0), _off(row_inv, HM),
-                                              _off(row_inv, 2 * HM), _p(o), _p(do), _p(stat[1:]), _p(delta), _off(dqkv, 0), _off(dqkv, d),
-                                              _off(dqkv, 2 * d), _p(lens), B, n_head, T, T, d3, d3, d3, d, d3, d3, d3, 1 if causal else 0,
-                                              0.125, drop_p, seed, ctx.ss, _p(_amax(do)), _p(am), _p(am), None, 1,
-                                              Mk, Mk, Bk * n_head * T, _stream()), "ttts_attention_bwd_img")
+        _attn_img_bwd(*(_img_operand(qkv, ctx.himg, c) for c in (0, d, 2 * d)), o, do, stat, delta,
+                      *((_off(dqkv, c), d3) for c in (0, d, 2 * d)), lens, B, n_head, T, T, causal, drop_p, seed, ctx.ss, am, am)
         dqkv._ttts_amax = am
-        return dqkv, None, None, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 def _dkv_query_splits(key_blocks: int, Tq: int) -> int:
@@ -1968,7 +1992,6 @@ class CrossAttentionImgFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, qh, kv, kvh, lens, n_head, drop_p, seed, need_weights=True, o_amax=None):
-        lib = _lib.load()
         q = _chk_window(q, "cross_attention.q")
         kv = _chk_window(kv, "cross_attention.kv")
         lens = _chk(lens, "cross_attention.lens", torch.int64)
@@ -1976,15 +1999,11 @@ class CrossAttentionImgFn(torch.autograd.Function):
         Tk = kv.shape[1]
         if kv.shape[2] != 2 * d or qh.row_inv.shape[1] < B * Tq or kvh.row_inv.shape[1] < B * Tk:
             raise ValueError("cross_attention: q / kv head images do not match")
-        ldq, ldk = q.stride(1), kv.stride(1)
         o = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
         stat = torch.empty(6, B, n_head, Tq, dtype=torch.float32, device=q.device)
         attn = torch.empty(B, n_head, Tq, Tk, dtype=torch.float32, device=q.device) if need_weights else None
-        _lib.check(lib.ttts_attention_fwd_img(_p(q), _off(kv, 0), _off(kv, d), qh.inv_of(0), kvh.inv_of(0), kvh.inv_of(d), _p(o),
-                                              _p(stat[0]), _p(attn), _p(lens), B, n_head, Tq, Tk, ldq, ldk, ldk, d, 0, 0.125,
-                                              float(drop_p), seed, _ss(), _p(kvh.amax_of(d)), _p(o_amax), _p(stat[1:]),
-                                              qh.row_inv.shape[1], kvh.row_inv.shape[1], 0, _stream()),
-                   "ttts_attention_fwd_img")
+        _attn_img_fwd(_img_operand(q, qh, 0), _img_operand(kv, kvh, 0), _img_operand(kv, kvh, d), o, stat, attn, lens, B, n_head,
+                      Tq, Tk, False, drop_p, seed, kvh.amax_of(d), o_amax)
         ctx.save_for_backward(q, kv, o, stat, lens)
         ctx.himg = (qh, kvh)
         ctx.cfg = (n_head, float(drop_p), seed)
@@ -1999,13 +2018,11 @@ class CrossAttentionImgFn(torch.autograd.Function):
     def backward(ctx, do, _dattn):
         if do is None:
             return (None,) * 10
-        lib = _lib.load()
         q, kv, o, stat, lens = ctx.saved_tensors
         qh, kvh = ctx.himg
         n_head, drop_p, seed = ctx.cfg
         B, Tq, d = q.shape
         Tk = kv.shape[1]
-        ldq, ldk = q.stride(1), kv.stride(1)
         do = _chk(do, "cross_attention.do")
         dq = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
         delta = torch.empty(B, n_head, Tq, dtype=torch.float32, device=q.device)
@@ -2020,110 +2037,62 @@ class CrossAttentionImgFn(torch.autograd.Function):
         # few key blocks and many queries (cross-attention: 256 workgroups of one 128-key block each): split the query range
         nsp = _dkv_query_splits(B * n_head * -(-Tk // 128), Tq)
         part = torch.empty(nsp, B, Tk, 2 * d, dtype=torch.float32, device=q.device) if nsp > 1 else None
-        _lib.check(lib.ttts_attention_bwd_img(_p(q), _off(kv, 0), _off(kv, d), qh.inv_of(0), kvh.inv_of(0), kvh.inv_of(d), _p(o), _p(do),
-                                              _p(stat[1:]), _p(delta), _p(dq), _off(dkv, 0), _off(dkv, d), _p(lens), B, n_head, Tq, Tk,
-                                              ldq, ldk, ldk, d, d, ldg, ldg, 0, 0.125, drop_p, seed, ctx.ss, _p(_amax(do)),
-                                              _p(am_q), _p(am_kv), _p(part), nsp, qh.row_inv.shape[1], kvh.row_inv.shape[1], 0,
-                                              _stream()), "ttts_attention_bwd_img")
+        _attn_img_bwd(_img_operand(q, qh, 0), _img_operand(kv, kvh, 0), _img_operand(kv, kvh, d), o, do, stat, delta,
+                      (_p(dq), d), (_off(dkv, 0), ldg), (_off(dkv, d), ldg), lens, B, n_head, Tq, Tk, False, drop_p, seed, ctx.ss,
+                      am_q, am_kv, part, nsp)
         dq._ttts_amax = am_q
         if slab is None:
             dkv._ttts_amax = am_kv
         return dq, None, dkv, None, None, None, None, None, None, None
 
 
-class SelfAttentionFn(torch.autograd.Function):
-    """o = softmax(mask(q k^T / sqrt(head_dim))) v over a packed in-proj output qkv (B,T,3d); head_dim <= 64 (heads of 64 are
-    read in place, narrower ones through zero-padded copies)."""
-
-    @staticmethod
-    def forward(ctx, qkv, lens, n_head, causal, drop_p, seed, qkv_amax=None, o_amax=None):
-        qkv = _chk(qkv, "self_attention.qkv")
-        lens = _chk(lens, "self_attention.lens", torch.int64)
-        B, T, d3 = qkv.shape
+def _attn_windows(q: torch.Tensor, kv: Optional[torch.Tensor]):
+    """-> (d, the (tensor, first column, row stride) windows of q, k and v): in q (B, Tq, d) and packed kv (B, Tk, 2d), or --
+    `kv is None` -- in one packed (B, T, 3d) projection `q`.  The gradient windows are the same windows of the gradient tensors."""
+    if kv is None:
+        d3 = q.shape[-1]
         d = d3 // 3
-        hd = _head_dim(d, n_head)
-        if qkv_amax is None:
-            qkv_amax = _amax(qkv)
-        pads = None
-        if hd == 64:
-            ptrs, ld = (_off(qkv, 0), _off(qkv, d), _off(qkv, 2 * d)), d3
-        else:
-            pads = tuple(_pad_heads(qkv, c, d3, B * T, n_head, hd) for c in (0, d, 2 * d))
-            ptrs, ld = tuple(_p(t) for t in pads), n_head * 64
-        o64, stat, _ = _attn_fwd(*ptrs, ld, ld, ld, B, n_head, T, T, lens, causal, drop_p, seed, False, qkv_amax, qkv_amax,
-                                 qkv_amax, o_amax, q_scale=hd ** -0.5)
-        if hd == 64:
-            o = o64
-        else:
-            o = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
-            _unpad_heads(o64, o, 0, d, B * T, n_head, hd)
-        ctx.save_for_backward(qkv, o64, stat, lens, *(pads or ()))
-        ctx.qkv_amax = qkv_amax
-        ctx.cfg = (n_head, causal, float(drop_p), seed, hd)
-        ctx.ss = _ss()
-        return o
+        return d, ((q, 0, d3), (q, d, d3), (q, 2 * d, d3))
+    d = q.shape[-1]
+    return d, ((q, 0, d), (kv, 0, 2 * d), (kv, d, 2 * d))
+
+
+class AttentionFn(torch.autograd.Function):
+    """o = softmax(mask(q k^T / sqrt(head_dim))) v on fp32 operands: q (B,Tq,d) and packed kv (B,Tk,2d) -- encoder-decoder
+    attention --, or, `kv is None`, a packed in-projection output q (B,T,3d) -- self-attention.  -> o (B,Tq,d) and the weights
+    (B,H,Tq,Tk) post-dropout (an empty tensor unless `need_weights`).  head_dim <= 64: heads of 64 are read in place, narrower
+    ones through zero-padded copies."""
 
     @staticmethod
-    def backward(ctx, do):
-        lib = _lib.load()
-        qkv, o64, stat, lens, *pads = ctx.saved_tensors
-        lse, rowstat = stat[0], stat[1:]
-        n_head, causal, drop_p, seed, hd = ctx.cfg
-        B, T, d3 = qkv.shape
-        d = d3 // 3
-        do = _chk(do, "self_attention.do")
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty(lse.shape, dtype=torch.float32, device=lse.device)
-        am = _amax_slots(qkv.device, True)                                     # max|dqkv| for the in-projection gradients
-        qa = ctx.qkv_amax
-        if hd == 64:
-            ins, ld, do64 = (_off(qkv, 0), _off(qkv, d), _off(qkv, 2 * d)), d3, do
-            outs, ldg = (_off(dqkv, 0), _off(dqkv, d), _off(dqkv, 2 * d)), d3
-        else:
-            ins, ld = tuple(_p(t) for t in pads), n_head * 64
-            do64 = _pad_heads(do, 0, d, B * T, n_head, hd)
-            grads = tuple(torch.empty(B * T, n_head * 64, dtype=torch.float32, device=qkv.device) for _ in range(3))
-            outs, ldg = tuple(_p(t) for t in grads), n_head * 64
-        _lib.check(_attn_bwd(lib, do64, am, am, qa, qa, qa, rowstat, *ins, _p(o64), _p(do64), _p(lse), _p(delta), *outs, _p(lens),
-                             B, n_head, T, T, ld, ld, ld, n_head * 64, ldg, ldg, ldg, 1 if causal else 0, hd ** -0.5, drop_p,
-                             seed, ctx.ss), "ttts_attention_bwd_h3")
-        if hd != 64:
-            for g, c in zip(grads, (0, d, 2 * d)):
-                _unpad_heads(g, dqkv, c, d3, B * T, n_head, hd)
-        dqkv._ttts_amax = am
-        return dqkv, None, None, None, None, None, None, None
-
-
-class CrossAttentionFn(torch.autograd.Function):
-    """Encoder-decoder attention: q (B,Tq,d), packed kv (B,Tk,2d) -> o (B,Tq,d), weights (B,H,Tq,Tk) post-dropout."""
-
-    @staticmethod
-    def forward(ctx, q, kv, lens, n_head, drop_p, seed, need_weights=True, q_amax=None, kv_amax=None, o_amax=None):
-        q = _chk(q, "cross_attention.q")
-        kv = _chk(kv, "cross_attention.kv")
-        lens = _chk(lens, "cross_attention.lens", torch.int64)
-        B, Tq, d = q.shape
-        Tk = kv.shape[1]
-        hd = _head_dim(d, n_head)
+    def forward(ctx, q, kv, lens, n_head, causal, drop_p, seed, need_weights, q_amax=None, kv_amax=None, o_amax=None):
+        q = _chk(q, "attention.q")
+        kv = _chk(kv, "attention.kv") if kv is not None else None
+        lens = _chk(lens, "attention.lens", torch.int64)
+        d, wins = _attn_windows(q, kv)
+        B, Tq, Tk = q.shape[0], q.shape[1], wins[1][0].shape[1]
+        hd = _head_width(d, n_head)
+        if hd > 64:
+            raise ValueError(f"attention kernels take head_dim <= 64 (d_model {d}, heads {n_head}: head_dim {hd})")
         q_amax = _amax(q) if q_amax is None else q_amax
-        kv_amax = _amax(kv) if kv_amax is None else kv_amax
-        pads = None
+        if kv is None:
+            kv_amax = q_amax             # one array describes the whole packed projection
+        elif kv_amax is None:
+            kv_amax = _amax(kv)
         if hd == 64:
-            ptrs, lds = (_off(q, 0), _off(kv, 0), _off(kv, d)), (d, 2 * d, 2 * d)
+            pads, ptrs, lds = (), [_off(t, c) for t, c, _ in wins], [ld for _, _, ld in wins]
         else:
-            pads = (_pad_heads(q, 0, d, B * Tq, n_head, hd), _pad_heads(kv, 0, 2 * d, B * Tk, n_head, hd),
-                    _pad_heads(kv, d, 2 * d, B * Tk, n_head, hd))
-            ptrs, lds = tuple(_p(t) for t in pads), (n_head * 64,) * 3
-        o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, False, drop_p, seed, need_weights, q_amax, kv_amax,
+            pads = tuple(_pad_heads(t, c, ld, B * t.shape[1], n_head, hd) for t, c, ld in wins)
+            ptrs, lds = [_p(t) for t in pads], [n_head * 64] * 3
+        o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_amax, kv_amax,
                                     kv_amax, o_amax, q_scale=hd ** -0.5)
         if hd == 64:
             o = o64
         else:
             o = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
             _unpad_heads(o64, o, 0, d, B * Tq, n_head, hd)
-        ctx.save_for_backward(q, kv, o64, stat, lens, *(pads or ()))
+        ctx.save_for_backward(q, kv, o64, stat, lens, *pads)
         ctx.amax = (q_amax, kv_amax)
-        ctx.cfg = (n_head, float(drop_p), seed, hd)
+        ctx.cfg = (n_head, causal, float(drop_p), seed, hd)
         ctx.ss = _ss()
         if attn is None:       # weights not requested: single-pass online softmax, nothing written
             attn = torch.empty(0, dtype=torch.float32, device=q.device)
@@ -2134,38 +2103,40 @@ class CrossAttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do, _dattn):
         if do is None:
-            return None, None, None, None, None, None, None, None, None, None
+            return (None,) * 11
         lib = _lib.load()
         q, kv, o64, stat, lens, *pads = ctx.saved_tensors
         lse, rowstat = stat[0], stat[1:]
-        n_head, drop_p, seed, hd = ctx.cfg
-        B, Tq, d = q.shape
-        Tk = kv.shape[1]
-        do = _chk(do, "cross_attention.do")
+        n_head, causal, drop_p, seed, hd = ctx.cfg
+        do = _chk(do, "attention.do")
         dq = torch.empty_like(q)
-        dkv = torch.empty_like(kv)
+        dkv = torch.empty_like(kv) if kv is not None else None
         delta = torch.empty(lse.shape, dtype=torch.float32, device=lse.device)
-        am_q, am_kv = _amax_slots(q.device, True), _amax_slots(q.device, True)
+        # max|dq|, max|dk, dv| for the in-projection gradients: ONE array for the one gradient of a packed projection
+        am_q = _amax_slots(q.device, True)
+        am_kv = _amax_slots(q.device, True) if kv is not None else am_q
         qa, kva = ctx.amax
+        d, wins = _attn_windows(q, kv)
+        _, gwins = _attn_windows(dq, dkv)
+        B, Tq, Tk = q.shape[0], q.shape[1], wins[1][0].shape[1]
         if hd == 64:
-            ins, lds, do64 = (_off(q, 0), _off(kv, 0), _off(kv, d)), (d, 2 * d, 2 * d), do
-            outs, ldg = (_off(dq, 0), _off(dkv, 0), _off(dkv, d)), (d, 2 * d, 2 * d)
+            ins, lds, do64 = [_off(t, c) for t, c, _ in wins], [ld for _, _, ld in wins], do
+            outs, ldg = [_off(t, c) for t, c, _ in gwins], [ld for _, _, ld in gwins]
         else:
-            ins, lds = tuple(_p(t) for t in pads), (n_head * 64,) * 3
+            ins, lds = [_p(t) for t in pads], [n_head * 64] * 3
             do64 = _pad_heads(do, 0, d, B * Tq, n_head, hd)
-            grads = (torch.empty(B * Tq, n_head * 64, dtype=torch.float32, device=q.device),
-                     torch.empty(B * Tk, n_head * 64, dtype=torch.float32, device=q.device),
-                     torch.empty(B * Tk, n_head * 64, dtype=torch.float32, device=q.device))
-            outs, ldg = tuple(_p(t) for t in grads), (n_head * 64,) * 3
+            grads = [torch.empty(B * t.shape[1], n_head * 64, dtype=torch.float32, device=q.device) for t, _, _ in gwins]
+            outs, ldg = [_p(t) for t in grads], [n_head * 64] * 3
         _lib.check(_attn_bwd(lib, do64, am_q, am_kv, qa, kva, kva, rowstat, *ins, _p(o64), _p(do64), _p(lse), _p(delta), *outs,
-                             _p(lens), B, n_head, Tq, Tk, *lds, n_head * 64, *ldg, 0, hd ** -0.5, drop_p, seed, ctx.ss),
-                   "ttts_attention_bwd_h3")
+                             _p(lens), B, n_head, Tq, Tk, *lds, n_head * 64, *ldg, 1 if causal else 0, hd ** -0.5, drop_p, seed,
+                             ctx.ss), "ttts_attention_bwd_h3")
         if hd != 64:
-            _unpad_heads(grads[0], dq, 0, d, B * Tq, n_head, hd)
-            _unpad_heads(grads[1], dkv, 0, 2 * d, B * Tk, n_head, hd)
-            _unpad_heads(grads[2], dkv, d, 2 * d, B * Tk, n_head, hd)
-        dq._ttts_amax, dkv._ttts_amax = am_q, am_kv
-        return dq, dkv, None, None, None, None, None, None, None, None
+            for g, (t, c, ld) in zip(grads, gwins):
+                _unpad_heads(g, t, c, ld, g.shape[0], n_head, hd)
+        dq._ttts_amax = am_q
+        if dkv is not None:
+            dkv._ttts_amax = am_kv
+        return dq, dkv, None, None, None, None, None, None, None, None, None
 
 
 def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: int):
@@ -2173,24 +2144,21 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
     returned); the partial maxima of a fp32 `qkv` ride on it when its producer left them (`linear(..., publish_amax=True)`), and
     the context leaves with its own for the out-projection."""
     d = qkv.shape[-1] // 3
-    if _wide_heads(d, n_head):
+    if _head_width(d, n_head) > 64:
         if isinstance(qkv, HeadImage):
             raise ValueError("self_attention: head images hold 64-column heads")
-        return _attention_wide_heads(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p)[0]
+        return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p)[0]
     if isinstance(qkv, HeadImage):             # the in-projection left a head image: the LDS-DMA kernels
         o_am = _amax_slots(qkv.device, True)
-        q_full = _twin(qkv.cells)
-        twin = [q_full, _twin(lens), []] if q_full is not None else None
-        o = SelfAttentionImgFn.apply(qkv.cells, qkv.row_inv, qkv.sec_amax, lens, n_head, causal, drop_p, seed, o_am, twin)
-        if twin is not None:
-            o._ttts_twin = twin[2][0]
+        twin = _twin_of(qkv.cells, lens)
+        o = _twin_attach(SelfAttentionImgFn.apply(qkv.cells, qkv, lens, n_head, causal, drop_p, seed, o_am, twin), twin)
         o._ttts_amax = o_am
         return o
     if _twin(qkv) is not None:
         raise ValueError("self_attention: a twin batch runs on head images only")
     am = _amax(qkv) if qkv.is_cuda else None
     o_am = _amax_slots(qkv.device, True) if qkv.is_cuda else None
-    o = SelfAttentionFn.apply(qkv, lens, n_head, causal, drop_p, seed, am, o_am)
+    o, _ = AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False, am, None, o_am)
     if o_am is not None:
         o._ttts_amax = o_am
     return o
@@ -2199,10 +2167,10 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
 def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_weights: bool = True):
     """q (B,Tq,d), kv (B,Tk,2d): both fp32 tensors, or both HeadImages (kv may be one layer's window of `cross_kv_projection`)"""
     d = q.shape[-1]
-    if _wide_heads(d, n_head):
+    if _head_width(d, n_head) > 64:
         if isinstance(q, HeadImage) or isinstance(kv, HeadImage):
             raise ValueError("cross_attention: head images hold 64-column heads")
-        o, attn = _attention_wide_heads(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p)
+        o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p)
         return o, (attn if need_weights else None)
     if isinstance(q, HeadImage) != isinstance(kv, HeadImage):
         raise ValueError("cross_attention: q and kv must both be head images or both fp32")
@@ -2213,7 +2181,7 @@ def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_wei
         return o, attn
     q_am, kv_am = (_amax(q), _amax(kv)) if q.is_cuda else (None, None)
     o_am = _amax_slots(q.device, True) if q.is_cuda else None
-    o, attn = CrossAttentionFn.apply(q, kv, lens, n_head, drop_p, seed, need_weights, q_am, kv_am, o_am)
+    o, attn = AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights, q_am, kv_am, o_am)
     if o_am is not None:
         o._ttts_amax = o_am
     return o, attn
@@ -2233,7 +2201,7 @@ class EmbeddingFn(torch.autograd.Function):
                    "ttts_embedding_fwd")
         out = out_k[:ids.shape[0]] if twin is not None else out_k
         if twin is not None:
-            twin[1].append(out_k)
+            twin.out = out_k
         ctx.save_for_backward(ids)
         ctx.shape = (vocab, d)
         ctx.sinks = _sinks(table)
@@ -2258,11 +2226,8 @@ class EmbeddingFn(torch.autograd.Function):
 
 def embedding(ids, table):
     out_am = _amax_slots(table.device, True) if table.is_cuda else None
-    i_full = _twin(ids)
-    twin = [i_full, []] if i_full is not None else None
-    out = EmbeddingFn.apply(ids, table, out_am, twin)
-    if twin is not None:
-        out._ttts_twin = twin[1][0]
+    twin = _twin_of(ids)
+    out = _twin_attach(EmbeddingFn.apply(ids, table, out_am, twin), twin)
     if out_am is not None:
         out._ttts_amax = out_am
     return out
@@ -2284,7 +2249,7 @@ class PosEncFn(torch.autograd.Function):
                                        _stream()), "ttts_posenc_fwd")
         y = y_k[:B] if twin is not None else y_k
         if twin is not None:
-            twin[1].append(y_k)
+            twin.out = y_k
         ctx.save_for_backward(pe)
         ctx.cfg = (float(drop_p), seed)
         ctx.ss = _ss()
@@ -2313,11 +2278,8 @@ class PosEncFn(torch.autograd.Function):
 
 def posenc(x, pe, alpha, drop_p: float, seed: int):
     y_am = _amax_slots(x.device, True) if x.is_cuda else None
-    x_full = _twin(x)
-    twin = [x_full, []] if x_full is not None else None
-    y = PosEncFn.apply(x, pe, alpha, drop_p, seed, y_am, twin)
-    if twin is not None:
-        y._ttts_twin = twin[1][0]
+    twin = _twin_of(x)
+    y = _twin_attach(PosEncFn.apply(x, pe, alpha, drop_p, seed, y_am, twin), twin)
     if y_am is not None:
         y._ttts_amax = y_am
     return y
