@@ -8,11 +8,14 @@ these same ops.  Pinned against the live reference by tests/golden/*.npz.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Optional
 
 import torch
 import torch.nn.functional as F
+
+from .dropmask import drop_scale
 
 Tensor = torch.Tensor
 
@@ -51,8 +54,54 @@ def _relu(x: Tensor) -> Tensor:
     return x * gate
 
 
-def _drop(x: Tensor, p: float, on: bool) -> Tensor:
-    return F.dropout(x, p, training=True) if (on and p > 0.0) else x
+class drop_masks:
+    """Test instrument for the dropout sites of the training forward, keyed by SITE NAME (`enc_prenet.0`, `enc.pe`,
+    `encoder.layers.0.attn` / `.attn_out` / `.ffn_h` / `.ffn_out`, `dec_prenet.1`, `dec.pe`, `decoder.layers.1.cross` /
+    `.cross_out`, `postnet.3`, ...; `drop_site_names(cfg)` lists them).
+
+    `with drop_masks(masks):` REPLACES F.dropout(x, p) at every site with p > 0 by x * keep * scale, `keep` the 0/1 tensor
+    `masks[site]` (any shape with the site's element count, in the site's own element order) and scale the float32
+    1 / (1 - p) the HIP kernels multiply by (`oracle.dropmask.drop_scale`; `scale=` overrides it for every site).  With the
+    masks another implementation drew, a dropout-on forward/backward is as continuous a comparison as a dropout-off one.  A
+    site that draws and has no mask is an error; `used` lists the sites that drew, in call order."""
+    active = None
+
+    def __init__(self, masks, scale: Optional[float] = None):
+        self.masks, self.scale, self.used = masks, scale, []
+
+    def __enter__(self):
+        self._prev, drop_masks.active = drop_masks.active, self
+        return self
+
+    def __exit__(self, *exc):
+        drop_masks.active = self._prev
+
+
+def drop_site_names(cfg: dict) -> List[str]:
+    """every dropout site of `oracle_forward`, in the oracle's call order"""
+    names = [f"enc_prenet.{i}" for i in range(cfg["encoder_prenet_n_layers"])] + ["enc.pe"]
+    for i in range(cfg["encoder_n_layers"]):
+        names += [f"encoder.layers.{i}.{s}" for s in ("attn", "attn_out", "ffn_h", "ffn_out")]
+    names += ["dec_prenet.0", "dec_prenet.1", "dec.pe"]
+    for i in range(cfg["decoder_n_layers"]):
+        names += [f"decoder.layers.{i}.{s}" for s in ("attn", "attn_out", "cross", "cross_out", "ffn_h", "ffn_out")]
+    return names + [f"postnet.{i}" for i in range(cfg["postnet_n_layers"])]
+
+
+def _drop(x: Tensor, p: float, on: bool, site: Optional[str] = None) -> Tensor:
+    if not (on and p > 0.0):
+        return x
+    dm = drop_masks.active
+    if dm is None:
+        return F.dropout(x, p, training=True)
+    if site is None or site not in dm.masks:
+        raise KeyError(f"drop_masks: dropout site {site!r} (p = {p}) draws and no mask was supplied for it")
+    keep = torch.as_tensor(dm.masks[site])
+    if keep.numel() != x.numel():
+        raise ValueError(f"drop_masks: the mask of {site!r} has {keep.numel()} elements, the site {x.numel()}")
+    dm.used.append(site)
+    scale = drop_scale(p) if dm.scale is None else dm.scale
+    return x * (keep.reshape(x.shape).to(x.dtype) * scale)
 
 
 def conv_norm_bn(sd, prefix: str, x: Tensor, training: bool, update_bn: bool) -> Tensor:
@@ -79,14 +128,14 @@ def conv_norm_bn(sd, prefix: str, x: Tensor, training: bool, update_bn: bool) ->
     return y.transpose(1, 2)
 
 
-def positional_encoding(sd, x: Tensor, p: float, drop_on: bool) -> Tensor:
+def positional_encoding(sd, x: Tensor, p: float, drop_on: bool, site: Optional[str] = None) -> Tensor:
     """PositionalEncoding.forward, model/model.py:91-97: x + alpha * pe[:T]; Dropout(0.1)."""
     x = x + sd["pe.alpha"] * sd["pe.pe"][: x.size(1), :].unsqueeze(0)
-    return _drop(x, p, drop_on)
+    return _drop(x, p, drop_on, site)
 
 
 def multi_head_attention(sd, prefix: str, xq: Tensor, xkv: Tensor, n_head: int,
-                         key_lens: Tensor, causal: bool, p: float, drop_on: bool):
+                         key_lens: Tensor, causal: bool, p: float, drop_on: bool, site: Optional[str] = None):
     """nn.MultiheadAttention as the reference calls it (model/layers.py:68-73; torch
     `F.multi_head_attention_forward`, torch/nn/functional.py:6206+): packed in-proj,
     q scaled by sqrt(1/head_dim) *before* q.k^T (:6578), additive -inf mask from the key
@@ -110,7 +159,7 @@ def multi_head_attention(sd, prefix: str, xq: Tensor, xkv: Tensor, n_head: int,
         dead = dead | torch.triu(torch.ones(Tq, Tk, dtype=torch.bool), diagonal=1).view(1, 1, Tq, Tk)
     s = s.masked_fill(dead, float("-inf"))
     a = torch.softmax(s, dim=-1)
-    a = _drop(a, p, drop_on)
+    a = _drop(a, p, drop_on, site)
     o = (a @ v).transpose(1, 2).reshape(B, Tq, d)
     o = F.linear(o, sd[f"{prefix}.out_proj.weight"], sd[f"{prefix}.out_proj.bias"])
     return o, a
@@ -118,8 +167,8 @@ def multi_head_attention(sd, prefix: str, xq: Tensor, xkv: Tensor, n_head: int,
 
 def _ffn(sd, prefix: str, x: Tensor, p: float, drop_on: bool) -> Tensor:
     """torch `_ff_block` (torch/nn/modules/transformer.py:980-982): W2 . Drop(relu(W1 x)), then Drop."""
-    h = _drop(_relu(F.linear(x, sd[f"{prefix}.linear1.weight"], sd[f"{prefix}.linear1.bias"])), p, drop_on)
-    return _drop(F.linear(h, sd[f"{prefix}.linear2.weight"], sd[f"{prefix}.linear2.bias"]), p, drop_on)
+    h = _drop(_relu(F.linear(x, sd[f"{prefix}.linear1.weight"], sd[f"{prefix}.linear1.bias"])), p, drop_on, f"{prefix}.ffn_h")
+    return _drop(F.linear(h, sd[f"{prefix}.linear2.weight"], sd[f"{prefix}.linear2.bias"]), p, drop_on, f"{prefix}.ffn_out")
 
 
 def _ln(sd, prefix: str, x: Tensor) -> Tensor:
@@ -128,18 +177,19 @@ def _ln(sd, prefix: str, x: Tensor) -> Tensor:
 
 def encoder_layer(sd, prefix, x, n_head, lens, p, drop_on):
     """Post-norm nn.TransformerEncoderLayer (torch/nn/modules/transformer.py:951-956)."""
-    sa, _ = multi_head_attention(sd, f"{prefix}.self_attn", x, x, n_head, lens, False, p, drop_on)
-    x = _ln(sd, f"{prefix}.norm1", x + _drop(sa, p, drop_on))
+    sa, _ = multi_head_attention(sd, f"{prefix}.self_attn", x, x, n_head, lens, False, p, drop_on, f"{prefix}.attn")
+    x = _ln(sd, f"{prefix}.norm1", x + _drop(sa, p, drop_on, f"{prefix}.attn_out"))
     x = _ln(sd, f"{prefix}.norm2", x + _ffn(sd, prefix, x, p, drop_on))
     return x
 
 
 def decoder_layer(sd, prefix, x, mem, n_head, mel_lens, ph_lens, p, drop_on):
     """TransformerDecoderLayer.forward post-norm branch, model/layers.py:46-50."""
-    sa, _ = multi_head_attention(sd, f"{prefix}.self_attn", x, x, n_head, mel_lens, True, p, drop_on)
-    x = _ln(sd, f"{prefix}.norm1", x + _drop(sa, p, drop_on))
-    ca, align = multi_head_attention(sd, f"{prefix}.multihead_attn", x, mem, n_head, ph_lens, False, p, drop_on)
-    x = _ln(sd, f"{prefix}.norm2", x + _drop(ca, p, drop_on))
+    sa, _ = multi_head_attention(sd, f"{prefix}.self_attn", x, x, n_head, mel_lens, True, p, drop_on, f"{prefix}.attn")
+    x = _ln(sd, f"{prefix}.norm1", x + _drop(sa, p, drop_on, f"{prefix}.attn_out"))
+    ca, align = multi_head_attention(sd, f"{prefix}.multihead_attn", x, mem, n_head, ph_lens, False, p, drop_on,
+                                     f"{prefix}.cross")
+    x = _ln(sd, f"{prefix}.norm2", x + _drop(ca, p, drop_on, f"{prefix}.cross_out"))
     x = _ln(sd, f"{prefix}.norm3", x + _ffn(sd, prefix, x, p, drop_on))
     return x, align
 
@@ -156,9 +206,9 @@ def oracle_forward(sd: Dict[str, Tensor], cfg: dict, phoneme: Tensor, melspec: T
     x = F.embedding(phoneme, sd["emb.weight"])
     for i in range(cfg["encoder_prenet_n_layers"]):          # EncoderPreNet, :38-45 (no activation)
         x = conv_norm_bn(sd, f"enc_prenet.layers.{2 * i}", x, training, update_bn)
-        x = _drop(x, cfg["encoder_prenet_dropout"], drop_on)
+        x = _drop(x, cfg["encoder_prenet_dropout"], drop_on, f"enc_prenet.{i}")
     x = F.linear(x, sd["enc_prenet.linear.linear.weight"], sd["enc_prenet.linear.linear.bias"])
-    x = positional_encoding(sd, x, 0.1, drop_on)
+    x = positional_encoding(sd, x, 0.1, drop_on, "enc.pe")
     for i in range(cfg["encoder_n_layers"]):
         x = encoder_layer(sd, f"encoder.layers.{i}", x, cfg["encoder_n_head"], phoneme_lens,
                           cfg["encoder_dropout"], drop_on)
@@ -166,10 +216,10 @@ def oracle_forward(sd: Dict[str, Tensor], cfg: dict, phoneme: Tensor, melspec: T
 
     # decoder side (:297-306); DecoderPreNet :65-66 has fixed dropout 0.5
     y = _drop(_relu(F.linear(tgt_in, sd["dec_prenet.linear1.linear.weight"],
-                              sd["dec_prenet.linear1.linear.bias"])), 0.5, drop_on)
+                              sd["dec_prenet.linear1.linear.bias"])), 0.5, drop_on, "dec_prenet.0")
     y = _drop(_relu(F.linear(y, sd["dec_prenet.linear2.linear.weight"],
-                              sd["dec_prenet.linear2.linear.bias"])), 0.5, drop_on)
-    y = positional_encoding(sd, y, 0.1, drop_on)
+                              sd["dec_prenet.linear2.linear.bias"])), 0.5, drop_on, "dec_prenet.1")
+    y = positional_encoding(sd, y, 0.1, drop_on, "dec.pe")
     aligns: List[Tensor] = []
     for i in range(cfg["decoder_n_layers"]):
         y, a = decoder_layer(sd, f"decoder.layers.{i}", y, memory, cfg["decoder_n_head"],
@@ -184,7 +234,7 @@ def oracle_forward(sd: Dict[str, Tensor], cfg: dict, phoneme: Tensor, melspec: T
         z = conv_norm_bn(sd, f"postnet.layers.{3 * i}", z, training, update_bn)
         if i < n_post - 1:
             z = torch.tanh(z)
-        z = _drop(z, cfg["postnet_dropout"], drop_on)
+        z = _drop(z, cfg["postnet_dropout"], drop_on, f"postnet.{i}")
     post = z + pred
     stop = F.linear(y, sd["linear2.linear.weight"], sd["linear2.linear.bias"]).squeeze(-1)
     return {"pred_melspec": pred, "post_melspec": post, "pred_stop": stop, "alignments": aligns}
@@ -250,16 +300,23 @@ def scheduled_sampling_mix(pred: Tensor, mel: Tensor, mel_lens: Tensor, p_tf: fl
 
 def oracle_training_step(sd, cfg, batch, epoch: int = 0, num_epochs: int = 300,
                          tf_mode: str = "linear", dropout: bool = False,
-                         stop_weight: float = 8.0, seed_u: Optional[Tensor] = None):
+                         stop_weight: float = 8.0, seed_u: Optional[Tensor] = None, masks=None,
+                         mask_scale: Optional[float] = None):
     """Arithmetic of LightningModule.training_step, lightning_module.py:45-86: no-grad forward
     (train mode: BN stats update) -> scheduled-sampling mix -> forward -> loss.  Returns the loss
-    dict and the second forward's outputs; the caller runs `.backward()` on loss['total']."""
+    dict and the second forward's outputs; the caller runs `.backward()` on loss['total'].
+    `masks`: None, or the two `drop_masks` dictionaries (no-grad forward's, grad forward's): both forwards then run with
+    dropout on under the given masks (`mask_scale`: the `scale` of `drop_masks`; None: float32 1 / (1 - p) per site)."""
     ph, mel, pl, ml = batch["phoneme"], batch["melspec"], batch["phoneme_lens"], batch["melspec_lens"]
-    with torch.no_grad():
+    if masks is not None:
+        dropout = True
+    first, second = (drop_masks(m, mask_scale) for m in masks) if masks is not None else (contextlib.nullcontext(),) * 2
+    with torch.no_grad(), first:
         pred = oracle_forward(sd, cfg, ph, mel, pl, ml, training=True, dropout=dropout)["pred_melspec"]
     p_tf = teacher_forcing_ratio(epoch + 1, num_epochs, tf_mode, cycles=1)
     mixed = scheduled_sampling_mix(pred, mel, ml, p_tf, seed_u)
-    out = oracle_forward(sd, cfg, ph, mixed, pl, ml, training=True, dropout=dropout)
+    with second:
+        out = oracle_forward(sd, cfg, ph, mixed, pl, ml, training=True, dropout=dropout)
     loss = oracle_loss(out, mel, ml, stop_weight)
     return loss, out, mixed
 

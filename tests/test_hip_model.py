@@ -23,18 +23,20 @@ FLIP_FREE_GATE_SCALED = 5e-5   # ... through the 12 layers of the scaled model (
 GRAD_GATE = 2e-3               # the tiny training_step surface test only (flips included; no flip observed there)
 
 
-def _oracle_gated_grads(cfg, w_seed, batch, gates, dtype=torch.float64):
-    """parameter gradients (and the loss) of the oracle evaluated in `dtype` with its ReLUs replaced by the given 0/1 gates"""
-    from oracle import fill_state, oracle_forward, oracle_loss, relu_gates
+def _oracle_gated_grads(cfg, w_seed, batch, gates, dtype=torch.float64, masks=None):
+    """parameter gradients (and the loss) of the oracle evaluated in `dtype` with its ReLUs replaced by the given 0/1 gates;
+    `masks`: None (dropout off), or the keep mask of every dropout site by name (oracle.drop_masks): dropout on, under them"""
+    import contextlib
+    from oracle import drop_masks, fill_state, oracle_forward, oracle_loss, relu_gates
     sd = fill_state(cfg, w_seed)
     for k in list(sd):
         if sd[k].is_floating_point():
             sd[k] = sd[k].to(dtype)
             if "running" not in k and k != "pe.pe":
                 sd[k].requires_grad_(True)
-    with relu_gates(gates=[g.to(dtype) for g in gates]):
+    with relu_gates(gates=[g.to(dtype) for g in gates]), (drop_masks(masks) if masks is not None else contextlib.nullcontext()):
         ref = oracle_forward(sd, cfg, batch["phoneme"], batch["melspec"].to(dtype), batch["phoneme_lens"], batch["melspec_lens"],
-                             training=True, dropout=False)
+                             training=True, dropout=masks is not None)
     loss = oracle_loss(ref, batch["melspec"].to(dtype), batch["melspec_lens"])
     loss["total"].backward()
     return {k: v.grad for k, v in sd.items() if v.requires_grad}, loss
@@ -49,14 +51,16 @@ def _no_dropout(m):
             mod.dropout = 0.0
 
 
-def _build(cfg_name, w_seed):
+def _build(cfg_name, w_seed, dropout=False):
+    """`dropout=True` keeps the configuration's dropout (tests/test_hip_dropout_parity.py)"""
     from oracle import model_config, fill_state
     from transformertts_amd.model import TransformerTTS
     cfg = model_config(cfg_name)
     m = TransformerTTS(**cfg, device="cuda")
     m.load_state_dict(fill_state(cfg, w_seed), strict=True)
     m = m.to("cuda")
-    _no_dropout(m)
+    if not dropout:
+        _no_dropout(m)
     return cfg, m
 
 

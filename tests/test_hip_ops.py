@@ -133,7 +133,9 @@ def test_conv_bn_fwd_bwd(B, T, cin, cout, act, training):
         assert int(nbt.item()) == 0 and torch.equal(rmg.cpu(), rm)
 
 
-@pytest.mark.parametrize("M,d", [(5, 128), (1000, 256), (333, 512), (7, 1024)])
+# (1025, 256), (4100, 512), (2049, 1024): past the 1024 rows one pass of the v4 backward's 256 blocks x 4 waves covers (its row
+# loop); (1500, 200): the general-width kernel past its block cap
+@pytest.mark.parametrize("M,d", [(5, 128), (1000, 256), (333, 512), (7, 1024), (1025, 256), (4100, 512), (2049, 1024), (1500, 200)])
 def test_layernorm(M, d):
     from transformertts_amd import ops
     x, g, b, dy = _rand(M, d, seed=1) * 2 + 0.3, 1 + _rand(d, seed=2, scale=0.2), _rand(d, seed=3, scale=0.1), _rand(M, d, seed=4)
@@ -156,7 +158,7 @@ def _image_decode(img, inv, M, K):
     return v * inv.double().view(M, 1)
 
 
-@pytest.mark.parametrize("M,d", [(777, 256), (130, 512), (65, 1024)])
+@pytest.mark.parametrize("M,d", [(777, 256), (130, 512), (65, 1024), (2050, 256)])
 def test_layernorm_backward_with_fused_dropout_backward(M, d):
     """ttts_layernorm_bwd_drop == ttts_layernorm_bwd followed by ttts_dropout_bwd on its dx, bit for bit (dx, the dropped
     copy, the parameter gradients), and the published maxima are those of the dropped copy."""
@@ -465,6 +467,95 @@ def test_dropout_masks_are_consistent_and_calibrated():
     (gkv,) = torch.autograd.grad(o1, kvg, do)
     v_grad_ref = torch.einsum("bhqk,bqhd->bkhd", a1, do.view(B, Tq, H, 64)).reshape(B, Tk, 128)
     assert rel_l2(gkv[:, :, 128:], v_grad_ref) < 1e-5
+
+
+@pytest.mark.parametrize("d", [128, 512])
+def test_embedding_backward_with_many_hits_per_id(d):
+    """ttts_embedding_bwd where the one small case of test_embedding_posenc_heads_add does not reach: V = 7 ids over n = 2600
+    positions -- three 1024-id steps (the last one partial), ~146 hits of every id per step, so the eight-rows-in-flight loop and
+    its remainder both run --, d = 512 (two column groups per thread), ids 0 and V - 1 present, and the gradient ADDED to a
+    non-zero table (accumulate = 1) next to the overwrite form.  fp64 reference, TOL."""
+    from transformertts_amd import _lib, ops
+    from transformertts_amd.ops import _p, _stream
+    lib, dev = _lib.load(), _dev()
+    V, n = 7, 2600
+    ids = torch.randint(0, V, (n,), generator=torch.Generator().manual_seed(1))
+    ids[0], ids[-1] = V - 1, 0
+    assert all(int((ids[s:s + 1024] == v).sum()) >= 8 for s in (0, 1024, 2048) for v in range(V))
+    tab, dout, base = _rand(V, d, seed=2), _rand(n, d, seed=3), _rand(V, d, seed=4)
+    td = tab.double().requires_grad_()
+    F.embedding(ids, td).backward(dout.double())
+    tg = _g(tab)
+    e = ops.EmbeddingFn.apply(ids.to(dev), tg)
+    e.backward(dout.to(dev))
+    assert torch.equal(e.cpu(), F.embedding(ids, tab)) and rel_l2(tg.grad, td.grad) < TOL
+    ids_d, dout_d = ids.to(dev), dout.to(dev)
+    for accumulate in (0, 1):
+        out = base.to(dev).clone()
+        assert lib.ttts_embedding_bwd(_p(ids_d), _p(dout_d), _p(out), n, V, d, accumulate, _stream()) == 0
+        want = td.grad + base.double() if accumulate else td.grad
+        assert rel_l2(out, want) < TOL, accumulate
+        assert rel_l2(out - (base.to(dev) if accumulate else 0.0), td.grad) < TOL, accumulate
+
+
+@pytest.mark.parametrize("M,d", [(4101, 256), (9000, 1024), (4101, 1024), (9000, 256), (1, 256), (5, 1024)])
+def test_rowdot_backward_rows_in_flight(M, d):
+    """ttts_rowdot_bwd (the stop head's backward) beyond the M = 63 of test_embedding_posenc_heads_add: M > 4096 = 4 rows x 1024
+    blocks -- the block cap, and the second row a wave holds in flight (at M = 4101 for five waves only, at 9000 for most, a
+    third trip for some) --, M = 1 and 5 as the ragged low end (one block, waves without a row); dx ADDED onto a non-zero
+    tensor (the mel head's data gradient in the model); dw, db overwritten and accumulated.  fp64 reference, TOL."""
+    from transformertts_amd import _lib, ops
+    from transformertts_amd.ops import _p, _stream
+    lib, dev = _lib.load(), _dev()
+    x, w, dy = _rand(M, d, seed=1), _rand(1, d, seed=2, scale=d ** -0.5), _rand(M, seed=3)
+    # (what dx already holds is of the size of what is added, so an error in the added part is not diluted)
+    dx0, dw0, db0 = _rand(M, d, seed=4, scale=d ** -0.5), _rand(1, d, seed=5), _rand(1, seed=6)
+    dx_ref = dx0.double() + dy.double()[:, None] * w.double()
+    dw_ref, db_ref = (dy.double()[:, None] * x.double()).sum(0, keepdim=True), dy.double().sum().view(1)
+    xg, wg, dyg = x.to(dev), w.to(dev), dy.to(dev)
+    nb = lib.ttts_rowdot_bwd_workspace_bytes(d)
+    for accumulate in (0, 1):
+        dx, dw, db, ws = dx0.to(dev).clone(), dw0.to(dev).clone(), db0.to(dev).clone(), ops._ws(nb, dev)
+        assert lib.ttts_rowdot_bwd(_p(dyg), _p(xg), _p(wg), _p(dx), _p(dw), _p(db), _p(ws), ws.numel() * 4, M, d, accumulate,
+                                   None, _stream()) == 0
+        assert rel_l2(dx, dx_ref) < TOL, accumulate
+        if accumulate:
+            assert rel_l2(dw, dw_ref + dw0.double()) < TOL
+            assert rel_l2(db, db_ref + db0.double()) < TOL
+        else:
+            assert rel_l2(dw, dw_ref) < TOL
+            assert rel_l2(db, db_ref) < TOL
+    # the autograd path (HeadsFn) at the same size: every gradient of both heads
+    wm, bm, bs = _rand(16, d, seed=7, scale=d ** -0.5), _rand(16, seed=8), _rand(1, seed=9)
+    dmel = _rand(M, 16, seed=10)
+    ps = [t.double().requires_grad_() for t in (x.view(1, M, d), wm, bm, w, bs)]
+    mel_r, stop_r = F.linear(ps[0], ps[1], ps[2]), F.linear(ps[0], ps[3], ps[4]).squeeze(-1)
+    (mel_r * dmel.double().view(1, M, 16)).sum().add((stop_r * dy.double().view(1, M)).sum()).backward()
+    gs = [_g(t) for t in (x.view(1, M, d), wm, bm, w, bs)]
+    mel, stop = ops.HeadsFn.apply(*gs)
+    ((mel * dmel.to(dev).view(1, M, 16)).sum() + (stop * dyg.view(1, M)).sum()).backward()
+    assert rel_l2(mel, mel_r) < TOL and rel_l2(stop, stop_r) < TOL
+    for a, b, name in zip(gs, ps, ("x", "w_mel", "b_mel", "w_stop", "b_stop")):
+        assert rel_l2(a.grad, b.grad) < TOL, name
+
+
+def test_posenc_backward_accumulates_alpha_gradient():
+    """ttts_posenc_bwd with accumulate = 1: d alpha is ADDED to what the sink holds (the model's one alpha serves two sites)"""
+    from oracle.spec import sinusoid_table
+    from transformertts_amd import _lib, ops
+    from transformertts_amd.ops import _p, _stream
+    lib, dev = _lib.load(), _dev()
+    B, T, d = 3, 21, 128
+    pe, dy = sinusoid_table(100, d), _rand(B, T, d, seed=3)
+    want = float((dy.double() * pe[:T].double().unsqueeze(0)).sum())
+    ped, dyd = pe.to(dev), dy.to(dev)
+    for accumulate, start in ((0, 7.5), (1, 7.5), (1, 0.0)):
+        dx, da = torch.empty_like(dyd), torch.full((1,), start, device=dev)
+        ws = ops._ws(lib.ttts_posenc_bwd_workspace_bytes(), dev)
+        assert lib.ttts_posenc_bwd(_p(dyd), _p(ped), _p(dx), _p(da), _p(ws), ws.numel() * 4, B, T, d, 0.0, 0, None, accumulate,
+                                   _stream()) == 0
+        assert torch.equal(dx, dyd)
+        assert rel_l2(da, torch.tensor([want + (start if accumulate else 0.0)])) < TOL, (accumulate, start)
 
 
 @pytest.mark.parametrize("B,T,C,lens", [(3, 37, 16, [37, 20, 9]), (4, 300, 80, [300, 211, 95, 1])])

@@ -960,6 +960,8 @@ class LinearFn(torch.autograd.Function):
             # the output leaves as a HEAD IMAGE (attention in-projections: ttts_linear_fwd_h3d_img); y_himg = (row_inv, section maxima,
             # columns per section).  `y` keeps its fp32 geometry and dtype, but its cells hold f16 hi / lo pairs: only the attention
             # kernels may read it (`linear` hands it out wrapped in a HeadImage, which is not a Tensor).
+            if act != ACT_NONE or float(drop_p) > 0.0 or r_ is not None:
+                raise ValueError("linear: a head-image output takes a bias-only epilogue (no activation, dropout or residual)")
             if x_amax is None:
                 x_amax = _amax(x)
             row_inv, sec_amax, sec_cols = y_himg
@@ -967,6 +969,7 @@ class LinearFn(torch.autograd.Function):
                                                    M, N, K, _p(x_amax), _p(sec_amax), sec_cols, _stream()), "ttts_linear_fwd_h3d_img")
         else:
             x_amax = _linear_fwd(x, w, b_, r_, y, M, N, K, x_amax, y_amax, (act, float(drop_p), seed, _ss(), row_shift, T), x_image)
+            _saw_drop("flat", seed, drop_p, (M, N))
         ctx.save_for_backward(x, w, y if act == ACT_RELU else None)
         ctx.cfg = (act, float(drop_p), seed, row_shift, T, b is not None, residual is not None)
         ctx.sinks = _sinks(w, b)
@@ -1050,6 +1053,16 @@ class LinearFn(torch.autograd.Function):
 
 # Test seam: called with the output of every relu-epilogue Linear, in call order (which units the HIP path gated off).
 _relu_observer = None
+# Test seam: called as (kind, seed, p, shape, half) for every kernel launch that draws a dropout mask (p > 0), in launch order.
+# kind "flat": element (row, col) of the (rows, N) output as stored is hashed at index row * N + col; kind "attn": weight
+# (row, key) of the (B * H * Tq, Tk) matrix.  A launch over a whole twin batch reports all 2 B utterances' rows (half None); a
+# launch over ONE half of a twin batch reports that half's rows and which half it is (0: the grad forward's).
+_drop_observer = None
+
+
+def _saw_drop(kind: str, seed: int, p: float, shape, half=None) -> None:
+    if _drop_observer is not None and float(p) > 0.0:
+        _drop_observer(kind, int(seed), float(p), tuple(int(v) for v in shape), half)
 
 
 class _ReluToken:
@@ -1566,6 +1579,7 @@ class ConvBNFn(torch.autograd.Function):
         z = torch.empty_like(y)
         _lib.check(lib.ttts_bn_apply_fwd(_p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(z), M, cout, act,
                                          float(drop_p), seed, _ss(), _p(z_amax), _stream()), "ttts_bn_apply_fwd")
+        _saw_drop("flat", seed, drop_p, (M, cout))
         ctx.save_for_backward(x, conv_w, y, mean, invstd, gamma, beta)
         ctx.x_amax = x_amax
         ctx.cfg = (training, act, float(drop_p), seed, conv_b is not None)
@@ -1631,6 +1645,7 @@ class ConvBNFn(torch.autograd.Function):
             seed_h = seed if (h == 0 or seed == 0) else ((seed * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF)
             _lib.check(lib.ttts_bn_apply_fwd(_p(y_h), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(z_h), M, cout, act,
                                              float(drop_p), seed_h, _ss(), _p(z_amax), _stream()), "ttts_bn_apply_fwd")
+            _saw_drop("flat", seed_h, drop_p, (M, cout), h)
         twin.out = z_k
         ctx.save_for_backward(x, conv_w, y_k[:B], mi[0, 0], mi[0, 1], gamma, beta)
         ctx.x_amax = x_amax
@@ -1916,6 +1931,7 @@ class SelfAttentionImgFn(torch.autograd.Function):
         stat = torch.empty(6, Bk, n_head, T, dtype=torch.float32, device=qkv.device)     # lse, then the five row-statistic planes
         _attn_img_fwd(*(_img_operand(qkv, himg, c) for c in (0, d, 2 * d)), o_k, stat, None, lens, Bk, n_head, T, T, causal,
                       drop_p, seed, himg.amax_of(2 * d), o_amax)
+        _saw_drop("attn", seed, drop_p, (Bk * n_head * T, T))
         o = o_k[:B] if twin is not None else o_k
         if twin is not None:
             twin.out = o_k
@@ -2004,6 +2020,7 @@ class CrossAttentionImgFn(torch.autograd.Function):
         attn = torch.empty(B, n_head, Tq, Tk, dtype=torch.float32, device=q.device) if need_weights else None
         _attn_img_fwd(_img_operand(q, qh, 0), _img_operand(kv, kvh, 0), _img_operand(kv, kvh, d), o, stat, attn, lens, B, n_head,
                       Tq, Tk, False, drop_p, seed, kvh.amax_of(d), o_amax)
+        _saw_drop("attn", seed, drop_p, (B * n_head * Tq, Tk))
         ctx.save_for_backward(q, kv, o, stat, lens)
         ctx.himg = (qh, kvh)
         ctx.cfg = (n_head, float(drop_p), seed)
@@ -2085,6 +2102,7 @@ class AttentionFn(torch.autograd.Function):
             ptrs, lds = [_p(t) for t in pads], [n_head * 64] * 3
         o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_amax, kv_amax,
                                     kv_amax, o_amax, q_scale=hd ** -0.5)
+        _saw_drop("attn", seed, drop_p, (B * n_head * Tq, Tk))
         if hd == 64:
             o = o64
         else:
@@ -2247,6 +2265,7 @@ class PosEncFn(torch.autograd.Function):
         y_k = torch.empty(k * B, T, d, dtype=torch.float32, device=x.device)
         _lib.check(lib.ttts_posenc_fwd(_p(x), _p(pe), _p(alpha), _p(y_k), k * B, T, d, float(drop_p), seed, _ss(), _p(y_amax),
                                        _stream()), "ttts_posenc_fwd")
+        _saw_drop("flat", seed, drop_p, (k * B * T, d))
         y = y_k[:B] if twin is not None else y_k
         if twin is not None:
             twin.out = y_k
