@@ -412,6 +412,32 @@ int ttts_attention_bwd_h3(const float* q, const float* k, const float* v, const 
                           int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, const float* do_amax,
                           float* dq_amax_out, float* dkv_amax_out, const float* q_amax, const float* k_amax,
                           const float* v_amax, const float* rowstat /* of the h3 forward, or NULL: use lse */, void* stream);
+/* ---- attention for heads of 65 .. 128 columns (ABI v17; attention_wide.hip): the same call sites as ttts_attention_fwd_h3 /
+ * ttts_attention_bwd_h3 -- encoder self-attention and decoder `_sa_block` (torch/nn/modules/transformer.py:961-978,1158-1175 ->
+ * F.scaled_dot_product_attention, torch/nn/functional.py:6629) and the decoder's `_mha_block` cross-attention with
+ * need_weights=True, average_attn_weights=False (model/layers.py:54-74; torch/nn/functional.py:6576-6610) -- in a model whose
+ * `nhead` leaves heads wider than 64 columns (the constructor takes any nhead that divides d_model, model/model.py:139-161).
+ * Same masks, dropout hash and edge conventions as ttts_attention_fwd; products on fp32 MFMA (exact fp32 products, no operand
+ * pre-scales).  q/k/v/o are addressed as ptr[(b*T + t)*ld + h*128 + c], so a packed in-projection output of 128-wide heads is
+ * read in place; heads of 65 .. 127 columns are zero-padded to 128 by ttts_heads_pad_w and passed with q_scale =
+ * sqrt(1 / head_dim).  rowstat: (2, B, H, Tq) floats, written by the forward and read by the backward: the final row maximum m
+ * of the masked, scaled scores (0 for a row without a live key) and the row sum l of exp(s - m).  The backward forms
+ * p = exp(s - m) / l as the forward did; a row whose l is exactly 1.0f is one-hot in fp32 and its score gradient is taken as
+ * zero (what torch's softmax backward gives; see ttts_attention_fwd_h3).  attn: NULL, or the (B,H,Tq,Tk) post-dropout weights
+ * (non-causal form only).  delta (B,H,Tq) is scratch.  A bad argument is refused before any launch with a message that names it
+ * (row strides that are no multiple of 4 floats or below H*128, drop_p outside [0, 1), non-positive sizes). */
+int ttts_attention_fwd_wide(const float* q, const float* k, const float* v, float* o, float* rowstat, float* attn,
+                            const int64_t* key_lens, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo,
+                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream);
+int ttts_attention_bwd_wide(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                            const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
+                            int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
+                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream);
+/* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
+ * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
+ * the kernels' own width. */
+int ttts_heads_pad_w(const float* src, int64_t ld_src, float* dst, int64_t rows, int H, int head_dim, int width, void* stream);
+int ttts_heads_unpad_w(const float* src, float* dst, int64_t ld_dst, int64_t rows, int H, int head_dim, int width, void* stream);
 /* ---- attention on head-image operands (ABI v11; attention_img.hip): the same call sites as ttts_attention_fwd_h3 /
  * ttts_attention_bwd_h3 (encoder self-attention and decoder `_sa_block`, torch/nn/modules/transformer.py:961-978,1158-1175 ->
  * torch/nn/functional.py:6629; the decoder's `_mha_block`, model/layers.py:54-74), head_dim 64.  q / k / v point at head 0 of

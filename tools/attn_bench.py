@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Self- / cross-attention forward and backward on the step's shapes through the ops layer (fp16x3 kernels), per-kernel
 times from HIP events around the forward and the backward call, and a check against fp64 torch (development aid).
-A/B two builds with TTTS_LIB=<lib>."""
-import os, sys
+A/B two builds with TTTS_LIB=<lib>.
+
+    --head-dim N (default 64): N > 64 runs the `wide` configuration's shapes (B=8, H=8; causal self T=870, self T=100, cross
+    870 x 100 WITH weights) on the 128-column fp32-MFMA kernels and, interleaved with them round by round in the same process,
+    on ops.masked_attention -- stock torch differentiated by autograd, the route these head widths took before the kernels
+    existed -- and prints forward + backward time and peak memory of both."""
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from transformertts_amd import ops
@@ -11,6 +16,50 @@ dev = torch.device("cuda:0")
 
 def ev():
     return torch.cuda.Event(enable_timing=True)
+
+
+def run_wide(name, B, H, hd, Tq, Tk, causal, need_w, p=0.1, rounds=5, reps=4):
+    """kernels against the torch route, alternating (A B A B ...): min and median of forward + backward, peak bytes above what
+    was live before the call"""
+    d = H * hd
+    torch.manual_seed(0)
+    lens = torch.full((B,), Tk, dtype=torch.int64, device=dev)
+    q = torch.randn(B, Tq, 3 * d if Tq == Tk else d, device=dev, requires_grad=True)
+    kv = None if Tq == Tk else torch.randn(B, Tk, 2 * d, device=dev, requires_grad=True)
+    do = torch.randn(B, Tq, d, device=dev)
+
+    def kernels():
+        if kv is None:
+            return ops.self_attention(q, lens, H, bool(causal), p, 7)
+        return ops.cross_attention(q, kv, lens, H, p, 7, need_w)[0]
+
+    def torch_route():
+        if kv is None:
+            return ops.masked_attention(q[..., :d], q[..., d:2 * d], q[..., 2 * d:], lens, H, bool(causal), p)[0]
+        return ops.masked_attention(q, kv[..., :d], kv[..., d:], lens, H, False, p)[0]
+
+    times, peak = {"kernels": [], "torch": []}, {}
+    for rnd in range(rounds + 1):                 # round 0 warms both up
+        for tag, fn in (("kernels", kernels), ("torch", torch_route)):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            for _ in range(reps):
+                e0, e1 = ev(), ev()
+                e0.record()
+                fn().backward(do)
+                e1.record()
+                torch.cuda.synchronize()
+                if rnd > 0:
+                    times[tag].append(e0.elapsed_time(e1) * 1e3)
+            peak[tag] = torch.cuda.max_memory_allocated() - base
+            q.grad = None
+            if kv is not None:
+                kv.grad = None
+    for tag in ("kernels", "torch"):
+        t = sorted(times[tag])
+        print(f"{name:12s} hd {hd} {tag:8s} fwd+bwd min {t[0]:8.1f} us  median {t[len(t) // 2]:8.1f} us   peak {peak[tag] / 2**20:8.1f} MiB",
+              flush=True)
 
 
 def run(name, B, H, Tq, Tk, causal, p=0.1, reps=8):
@@ -53,6 +102,14 @@ def run(name, B, H, Tq, Tk, causal, p=0.1, reps=8):
     print(f"{name:10s} fwd {min(tf):7.1f} us  bwd {min(tb):7.1f} us   fwd rel err vs fp64 {err:.1e}", flush=True)
 
 
-run("dec self", 64, 4, 870, 870, 1)
-run("enc self", 64, 4, 100, 100, 0)
-run("cross", 64, 4, 870, 100, 0)
+ap = argparse.ArgumentParser()
+ap.add_argument("--head-dim", type=int, default=64)
+args = ap.parse_args()
+if args.head_dim > 64:
+    run_wide("causal self", 8, 8, args.head_dim, 870, 870, 1, False)
+    run_wide("self", 8, 8, args.head_dim, 100, 100, 0, False)
+    run_wide("cross+weights", 8, 8, args.head_dim, 870, 100, 0, True)
+else:
+    run("dec self", 64, 4, 870, 870, 1)
+    run("enc self", 64, 4, 100, 100, 0)
+    run("cross", 64, 4, 870, 100, 0)

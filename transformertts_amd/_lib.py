@@ -83,8 +83,12 @@ SIGNATURES = {
     "ttts_attention_fwd_img": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U, P, P, P, P, L, L, L, P]),
     "ttts_attention_bwd_img": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, P, P, P,
                                    P, I, L, L, L, P]),
+    "ttts_attention_fwd_wide": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U, P, P]),
+    "ttts_attention_bwd_wide": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
+    "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),
+    "ttts_heads_unpad_w": (I, [P, P, L, L, I, I, I, P]),
     "ttts_embedding_fwd": (I, [P, P, P, L, I, I, P, P]),
     "ttts_embedding_bwd": (I, [P, P, P, L, I, I, I, P]),
     "ttts_posenc_fwd": (I, [P, P, P, P, I, I, I, F, U, P, P, P]),

@@ -53,13 +53,14 @@ int launch_zero(void* p, size_t nbytes, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------ head padding (attention for head_dim < 64)
-// dst[r][h*64 + c] = c < hd ? src[r*ld_src + h*hd + c] : 0   (pad)      dst[r*ld_dst + h*hd + c] = src[r][h*64 + c]   (unpad)
+// dst[r][h*W + c] = c < hd ? src[r*ld_src + h*hd + c] : 0   (pad)      dst[r*ld_dst + h*hd + c] = src[r][h*W + c]   (unpad)
+template <int W>   // padded width: 64, or 128 (heads of 65 .. 128 columns, attention_wide.hip)
 __global__ __launch_bounds__(256) void heads_pad_kernel(const float* __restrict__ src, long ld_src, float* __restrict__ dst,
                                                         long rows, int H, int hd, int unpad, long ld_dst) {
-    const long n = rows * H * 64;
+    const long n = rows * H * W;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i & 63);
-        const long rh = i >> 6;
+        const int c = (int)(i & (W - 1));
+        const long rh = i / W;
         const int h = (int)(rh % H);
         const long r = rh / H;
         if (unpad) {
@@ -375,14 +376,14 @@ using namespace ttts;
 extern "C" {
 
 const char* ttts_last_error(void) { return ttts::g_err; }
-int ttts_abi_version(void) { return 16; }
+int ttts_abi_version(void) { return 17; }
 
 int ttts_zero(void* p, size_t nbytes, void* stream) { return ::ttts::launch_zero(p, nbytes, (hipStream_t)stream); }
 
 int ttts_heads_pad(const float* src, int64_t ld_src, float* dst, int64_t rows, int H, int head_dim, void* stream) {
     TTTS_REQUIRE(src && dst && rows > 0 && H > 0 && head_dim > 0 && head_dim <= 64 && ld_src >= (int64_t)H * head_dim,
                  "heads_pad: bad arguments (head_dim %d must be in 1..64)", head_dim);
-    hipLaunchKernelGGL(heads_pad_kernel, dim3(ew_grid(rows * H * 64)), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, dst,
+    hipLaunchKernelGGL(heads_pad_kernel<64>, dim3(ew_grid(rows * H * 64)), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, dst,
                        (long)rows, H, head_dim, 0, 0L);
     TTTS_LAUNCH_CHECK("heads_pad_kernel");
     return TTTS_OK;
@@ -391,8 +392,30 @@ int ttts_heads_pad(const float* src, int64_t ld_src, float* dst, int64_t rows, i
 int ttts_heads_unpad(const float* src, float* dst, int64_t ld_dst, int64_t rows, int H, int head_dim, void* stream) {
     TTTS_REQUIRE(src && dst && rows > 0 && H > 0 && head_dim > 0 && head_dim <= 64 && ld_dst >= (int64_t)H * head_dim,
                  "heads_unpad: bad arguments (head_dim %d must be in 1..64)", head_dim);
-    hipLaunchKernelGGL(heads_pad_kernel, dim3(ew_grid(rows * H * 64)), dim3(256), 0, (hipStream_t)stream, src, 0L, dst, (long)rows,
+    hipLaunchKernelGGL(heads_pad_kernel<64>, dim3(ew_grid(rows * H * 64)), dim3(256), 0, (hipStream_t)stream, src, 0L, dst, (long)rows,
                        H, head_dim, 1, (long)ld_dst);
+    TTTS_LAUNCH_CHECK("heads_pad_kernel");
+    return TTTS_OK;
+}
+
+int ttts_heads_pad_w(const float* src, int64_t ld_src, float* dst, int64_t rows, int H, int head_dim, int width, void* stream) {
+    TTTS_REQUIRE(width == 64 || width == 128, "heads_pad_w: width %d must be 64 or 128", width);
+    if (width == 64) return ttts_heads_pad(src, ld_src, dst, rows, H, head_dim, stream);
+    TTTS_REQUIRE(src && dst && rows > 0 && H > 0 && head_dim > 0 && head_dim <= 128 && ld_src >= (int64_t)H * head_dim,
+                 "heads_pad_w: bad arguments (head_dim %d must be in 1..128)", head_dim);
+    hipLaunchKernelGGL(heads_pad_kernel<128>, dim3(ew_grid(rows * H * 128)), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src,
+                       dst, (long)rows, H, head_dim, 0, 0L);
+    TTTS_LAUNCH_CHECK("heads_pad_kernel");
+    return TTTS_OK;
+}
+
+int ttts_heads_unpad_w(const float* src, float* dst, int64_t ld_dst, int64_t rows, int H, int head_dim, int width, void* stream) {
+    TTTS_REQUIRE(width == 64 || width == 128, "heads_unpad_w: width %d must be 64 or 128", width);
+    if (width == 64) return ttts_heads_unpad(src, dst, ld_dst, rows, H, head_dim, stream);
+    TTTS_REQUIRE(src && dst && rows > 0 && H > 0 && head_dim > 0 && head_dim <= 128 && ld_dst >= (int64_t)H * head_dim,
+                 "heads_unpad_w: bad arguments (head_dim %d must be in 1..128)", head_dim);
+    hipLaunchKernelGGL(heads_pad_kernel<128>, dim3(ew_grid(rows * H * 128)), dim3(256), 0, (hipStream_t)stream, src, 0L, dst,
+                       (long)rows, H, head_dim, 1, (long)ld_dst);
     TTTS_LAUNCH_CHECK("heads_pad_kernel");
     return TTTS_OK;
 }

@@ -103,7 +103,8 @@ def _lens_and_kpm(lens: Optional[Tensor], kpm: Optional[Tensor], B: int, T: int,
 
 class MultiheadAttention(nn.Module):
     """Parameter layout of nn.MultiheadAttention (packed in-proj, `out_proj` sub-module).  Heads of 64 columns run on the
-    head-image kernels, narrower ones on the padded fp32 kernels, wider ones as tensor algebra (ops.masked_attention)."""
+    head-image kernels, narrower ones on the padded fp32 kernels, heads of 65 .. 128 columns on the 128-column fp32-MFMA kernels
+    (csrc/attention_wide.hip: same masks, dropout sites and seeds), wider ones as tensor algebra (ops.masked_attention)."""
 
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0):
         super().__init__()

@@ -1820,6 +1820,24 @@ def _attn_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, 
     return o, stat, attn
 
 
+def _attn_wide_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_scale: float):
+    """Heads of 128 columns on the fp32-MFMA kernels of csrc/attention_wide.hip (no operand maxima: exact fp32 products).
+    -> (o (B, Tq, H * 128), stat, attn); stat (2, B, H, Tq) = the row maxima and row sums the backward re-forms the weights from."""
+    dev = lens.device
+    o = torch.empty(B, Tq, H * 128, dtype=torch.float32, device=dev)
+    stat = torch.empty(2, B, H, Tq, dtype=torch.float32, device=dev)
+    attn = torch.empty(B, H, Tq, Tk, dtype=torch.float32, device=dev) if need_weights else None
+    _lib.check(_lib.load().ttts_attention_fwd_wide(q, k, v, _p(o), _p(stat), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv,
+                                                   H * 128, 1 if causal else 0, float(q_scale), float(drop_p), seed, _ss(),
+                                                   _stream()), "ttts_attention_fwd_wide")
+    return o, stat, attn
+
+
+def _attn_wide_bwd(*args) -> None:
+    """Backward of `_attn_wide_fwd`; `args` = every C-ABI argument up to step_seed."""
+    _lib.check(_lib.load().ttts_attention_bwd_wide(*args, _stream()), "ttts_attention_bwd_wide")
+
+
 def _off(t: torch.Tensor, col: int):
     return c_void_p(t.data_ptr() + 4 * col)
 
@@ -1858,8 +1876,9 @@ def _attn_img_bwd(q, k, v, o, do, stat, delta, dq, dk, dv, lens, B, H, Tq, Tk, c
 
 
 def _head_width(d: int, n_head: int) -> int:
-    """Columns per head.  The kernels work on 64-column heads: narrower ones are zero-padded to 64 (`_pad_heads`), wider ones
-    do not reach them (`masked_attention`)."""
+    """Columns per head.  The kernels work on 64-column heads (narrower ones are zero-padded to 64, `_pad_heads`) and, for
+    heads of 65 .. 128 columns, on 128-column heads (csrc/attention_wide.hip; narrower ones zero-padded to 128); heads wider
+    than 128 do not reach them (`masked_attention`)."""
     if n_head <= 0 or d % n_head != 0:
         raise ValueError(f"attention: d_model {d} is not divisible by {n_head} heads")
     return d // n_head
@@ -1868,8 +1887,8 @@ def _head_width(d: int, n_head: int) -> int:
 def masked_attention(q, k, v, lens, n_head: int, causal: bool, drop_p: float, dead=None, add_mask=None):
     """(context, per-head weights): attention as plain tensor algebra on the library's fp32 GEMMs, for the two cases the
     hand-written kernels do not take:
-      * heads wider than 64 columns (the reference takes any `nhead`, model/model.py:139-161; no BASELINE configuration has them):
-        the kernels hold a 64-column head per fragment set;
+      * heads wider than 128 columns (the reference takes any `nhead`, model/model.py:139-161; no BASELINE configuration has
+        them): the kernels hold a head of at most 128 columns per lane;
       * masks that are not "keys past a length" / causal (a key-padding mask with holes, `memory_mask`, an arbitrary `tgt_mask` /
         `mask` -- arguments of the reference's layers, model/layers.py:29-74, that its model never passes).
     Same conventions as the kernels (weights returned AFTER dropout, rows without an allowed key give zeros), differentiated by
@@ -1900,15 +1919,16 @@ def masked_attention(q, k, v, lens, n_head: int, causal: bool, drop_p: float, de
     return o, p
 
 
-def _pad_heads(src: torch.Tensor, col0: int, ld: int, rows: int, H: int, hd: int) -> torch.Tensor:
-    """(rows, H*64): the H heads of `src` (row stride ld floats, head h at column col0 + h*hd) zero-padded to 64 columns."""
-    dst = torch.empty(rows, H * 64, dtype=torch.float32, device=src.device)
-    _lib.check(_lib.load().ttts_heads_pad(_off(src, col0), ld, _p(dst), rows, H, hd, _stream()), "ttts_heads_pad")
+def _pad_heads(src: torch.Tensor, col0: int, ld: int, rows: int, H: int, hd: int, width: int = 64) -> torch.Tensor:
+    """(rows, H*width): the H heads of `src` (row stride ld floats, head h at column col0 + h*hd) zero-padded to `width` (64 or
+    128) columns."""
+    dst = torch.empty(rows, H * width, dtype=torch.float32, device=src.device)
+    _lib.check(_lib.load().ttts_heads_pad_w(_off(src, col0), ld, _p(dst), rows, H, hd, width, _stream()), "ttts_heads_pad_w")
     return dst
 
 
-def _unpad_heads(src: torch.Tensor, dst: torch.Tensor, col0: int, ld: int, rows: int, H: int, hd: int) -> None:
-    _lib.check(_lib.load().ttts_heads_unpad(_p(src), _off(dst, col0), ld, rows, H, hd, _stream()), "ttts_heads_unpad")
+def _unpad_heads(src: torch.Tensor, dst: torch.Tensor, col0: int, ld: int, rows: int, H: int, hd: int, width: int = 64) -> None:
+    _lib.check(_lib.load().ttts_heads_unpad_w(_p(src), _off(dst, col0), ld, rows, H, hd, width, _stream()), "ttts_heads_unpad_w")
 
 
 class SelfAttentionImgFn(torch.autograd.Function):
@@ -2077,8 +2097,11 @@ def _attn_windows(q: torch.Tensor, kv: Optional[torch.Tensor]):
 class AttentionFn(torch.autograd.Function):
     """o = softmax(mask(q k^T / sqrt(head_dim))) v on fp32 operands: q (B,Tq,d) and packed kv (B,Tk,2d) -- encoder-decoder
     attention --, or, `kv is None`, a packed in-projection output q (B,T,3d) -- self-attention.  -> o (B,Tq,d) and the weights
-    (B,H,Tq,Tk) post-dropout (an empty tensor unless `need_weights`).  head_dim <= 64: heads of 64 are read in place, narrower
-    ones through zero-padded copies."""
+    (B,H,Tq,Tk) post-dropout (an empty tensor unless `need_weights`).  head_dim <= 64: the fp16x3 kernels on 64-column heads
+    (heads of 64 are read in place, narrower ones through zero-padded copies).  64 < head_dim <= 128: the fp32-MFMA kernels on
+    128-column heads (csrc/attention_wide.hip; 128 in place, narrower through copies padded to 128), which take no operand
+    maxima and publish none.  Saved for backward at either width: the operands, o, the row statistics, the lengths and the
+    padded copies -- never the weights."""
 
     @staticmethod
     def forward(ctx, q, kv, lens, n_head, causal, drop_p, seed, need_weights, q_amax=None, kv_amax=None, o_amax=None):
@@ -2088,26 +2111,33 @@ class AttentionFn(torch.autograd.Function):
         d, wins = _attn_windows(q, kv)
         B, Tq, Tk = q.shape[0], q.shape[1], wins[1][0].shape[1]
         hd = _head_width(d, n_head)
-        if hd > 64:
-            raise ValueError(f"attention kernels take head_dim <= 64 (d_model {d}, heads {n_head}: head_dim {hd})")
-        q_amax = _amax(q) if q_amax is None else q_amax
-        if kv is None:
-            kv_amax = q_amax             # one array describes the whole packed projection
-        elif kv_amax is None:
-            kv_amax = _amax(kv)
-        if hd == 64:
+        if hd > 128:
+            raise ValueError(f"attention kernels take head_dim <= 128 (d_model {d}, heads {n_head}: head_dim {hd})")
+        W = 64 if hd <= 64 else 128      # columns per head as the kernels see them
+        if W == 128:
+            q_amax = kv_amax = None      # exact fp32 products: no pre-scales
+        else:
+            q_amax = _amax(q) if q_amax is None else q_amax
+            if kv is None:
+                kv_amax = q_amax         # one array describes the whole packed projection
+            elif kv_amax is None:
+                kv_amax = _amax(kv)
+        if hd == W:
             pads, ptrs, lds = (), [_off(t, c) for t, c, _ in wins], [ld for _, _, ld in wins]
         else:
-            pads = tuple(_pad_heads(t, c, ld, B * t.shape[1], n_head, hd) for t, c, ld in wins)
-            ptrs, lds = [_p(t) for t in pads], [n_head * 64] * 3
-        o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_amax, kv_amax,
-                                    kv_amax, o_amax, q_scale=hd ** -0.5)
+            pads = tuple(_pad_heads(t, c, ld, B * t.shape[1], n_head, hd, W) for t, c, ld in wins)
+            ptrs, lds = [_p(t) for t in pads], [n_head * W] * 3
+        if W == 128:
+            o64, stat, attn = _attn_wide_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, hd ** -0.5)
+        else:
+            o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_amax,
+                                        kv_amax, kv_amax, o_amax, q_scale=hd ** -0.5)
         _saw_drop("attn", seed, drop_p, (B * n_head * Tq, Tk))
-        if hd == 64:
+        if hd == W:
             o = o64
         else:
             o = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
-            _unpad_heads(o64, o, 0, d, B * Tq, n_head, hd)
+            _unpad_heads(o64, o, 0, d, B * Tq, n_head, hd, W)
         ctx.save_for_backward(q, kv, o64, stat, lens, *pads)
         ctx.amax = (q_amax, kv_amax)
         ctx.cfg = (n_head, causal, float(drop_p), seed, hd)
@@ -2124,36 +2154,41 @@ class AttentionFn(torch.autograd.Function):
             return (None,) * 11
         lib = _lib.load()
         q, kv, o64, stat, lens, *pads = ctx.saved_tensors
-        lse, rowstat = stat[0], stat[1:]
         n_head, causal, drop_p, seed, hd = ctx.cfg
+        W = 64 if hd <= 64 else 128
         do = _chk(do, "attention.do")
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv) if kv is not None else None
-        delta = torch.empty(lse.shape, dtype=torch.float32, device=lse.device)
-        # max|dq|, max|dk, dv| for the in-projection gradients: ONE array for the one gradient of a packed projection
-        am_q = _amax_slots(q.device, True)
-        am_kv = _amax_slots(q.device, True) if kv is not None else am_q
-        qa, kva = ctx.amax
+        delta = torch.empty(stat.shape[1:], dtype=torch.float32, device=stat.device)
         d, wins = _attn_windows(q, kv)
         _, gwins = _attn_windows(dq, dkv)
         B, Tq, Tk = q.shape[0], q.shape[1], wins[1][0].shape[1]
-        if hd == 64:
+        if hd == W:
             ins, lds, do64 = [_off(t, c) for t, c, _ in wins], [ld for _, _, ld in wins], do
             outs, ldg = [_off(t, c) for t, c, _ in gwins], [ld for _, _, ld in gwins]
         else:
-            ins, lds = [_p(t) for t in pads], [n_head * 64] * 3
-            do64 = _pad_heads(do, 0, d, B * Tq, n_head, hd)
-            grads = [torch.empty(B * t.shape[1], n_head * 64, dtype=torch.float32, device=q.device) for t, _, _ in gwins]
-            outs, ldg = [_p(t) for t in grads], [n_head * 64] * 3
-        _lib.check(_attn_bwd(lib, do64, am_q, am_kv, qa, kva, kva, rowstat, *ins, _p(o64), _p(do64), _p(lse), _p(delta), *outs,
-                             _p(lens), B, n_head, Tq, Tk, *lds, n_head * 64, *ldg, 1 if causal else 0, hd ** -0.5, drop_p, seed,
-                             ctx.ss), "ttts_attention_bwd_h3")
-        if hd != 64:
+            ins, lds = [_p(t) for t in pads], [n_head * W] * 3
+            do64 = _pad_heads(do, 0, d, B * Tq, n_head, hd, W)
+            grads = [torch.empty(B * t.shape[1], n_head * W, dtype=torch.float32, device=q.device) for t, _, _ in gwins]
+            outs, ldg = [_p(t) for t in grads], [n_head * W] * 3
+        if W == 128:
+            _attn_wide_bwd(*ins, _p(o64), _p(do64), _p(stat), _p(delta), *outs, _p(lens), B, n_head, Tq, Tk, *lds, n_head * W,
+                           *ldg, 1 if causal else 0, hd ** -0.5, drop_p, seed, ctx.ss)
+        else:
+            lse, rowstat = stat[0], stat[1:]
+            # max|dq|, max|dk, dv| for the in-projection gradients: ONE array for the one gradient of a packed projection
+            am_q = _amax_slots(q.device, True)
+            am_kv = _amax_slots(q.device, True) if kv is not None else am_q
+            qa, kva = ctx.amax
+            _lib.check(_attn_bwd(lib, do64, am_q, am_kv, qa, kva, kva, rowstat, *ins, _p(o64), _p(do64), _p(lse), _p(delta),
+                                 *outs, _p(lens), B, n_head, Tq, Tk, *lds, n_head * 64, *ldg, 1 if causal else 0, hd ** -0.5,
+                                 drop_p, seed, ctx.ss), "ttts_attention_bwd_h3")
+            dq._ttts_amax = am_q
+            if dkv is not None:
+                dkv._ttts_amax = am_kv
+        if hd != W:
             for g, (t, c, ld) in zip(grads, gwins):
-                _unpad_heads(g, t, c, ld, g.shape[0], n_head, hd)
-        dq._ttts_amax = am_q
-        if dkv is not None:
-            dkv._ttts_amax = am_kv
+                _unpad_heads(g, t, c, ld, g.shape[0], n_head, hd, W)
         return dq, dkv, None, None, None, None, None, None, None, None, None
 
 
@@ -2162,10 +2197,15 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
     returned); the partial maxima of a fp32 `qkv` ride on it when its producer left them (`linear(..., publish_amax=True)`), and
     the context leaves with its own for the out-projection."""
     d = qkv.shape[-1] // 3
-    if _head_width(d, n_head) > 64:
+    hd = _head_width(d, n_head)
+    if hd > 64:
         if isinstance(qkv, HeadImage):
             raise ValueError("self_attention: head images hold 64-column heads")
-        return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p)[0]
+        if hd > 128:
+            return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p)[0]
+        if _twin(qkv) is not None:
+            raise ValueError("self_attention: a twin batch runs on head images only")
+        return AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False)[0]     # 128-column kernels: no maxima
     if isinstance(qkv, HeadImage):             # the in-projection left a head image: the LDS-DMA kernels
         o_am = _amax_slots(qkv.device, True)
         twin = _twin_of(qkv.cells, lens)
@@ -2185,11 +2225,14 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
 def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_weights: bool = True):
     """q (B,Tq,d), kv (B,Tk,2d): both fp32 tensors, or both HeadImages (kv may be one layer's window of `cross_kv_projection`)"""
     d = q.shape[-1]
-    if _head_width(d, n_head) > 64:
+    hd = _head_width(d, n_head)
+    if hd > 64:
         if isinstance(q, HeadImage) or isinstance(kv, HeadImage):
             raise ValueError("cross_attention: head images hold 64-column heads")
-        o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p)
-        return o, (attn if need_weights else None)
+        if hd > 128:
+            o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p)
+            return o, (attn if need_weights else None)
+        return AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights)     # 128-column kernels: no maxima
     if isinstance(q, HeadImage) != isinstance(kv, HeadImage):
         raise ValueError("cross_attention: q and kv must both be head images or both fp32")
     if isinstance(q, HeadImage):
