@@ -1,5 +1,6 @@
-"""The 128-column attention entry points (ABI v17, csrc/attention_wide.hip): declared, exported, and their argument checks --
-host logic only, no GPU (every refusal happens before a launch)."""
+"""The 128-column attention entry points (ABI v17, csrc/attention_wide.hip): declared, exported, and their argument checks -- and
+the same refusal table for the 64-column families, whose check they share.  Host logic only, no GPU (every refusal happens
+before a launch)."""
 import ctypes
 import os
 import re
@@ -26,6 +27,8 @@ def test_abi_version_and_the_header_declares_the_wide_entry_points():
 
 
 def test_wide_entry_points_refuse_bad_arguments_with_a_message():
+    """One refusal table for every attention family (one check serves them all, csrc/attention_common.h): the 128-column entry
+    points and the 64-column fp32-MFMA, bf16x6, fp16x3 and head-image ones."""
     from transformertts_amd import _lib
     lib = _lib.load()
     buf = ctypes.create_string_buffer(4096 + 16)
@@ -36,37 +39,76 @@ def test_wide_entry_points_refuse_bad_arguments_with_a_message():
         assert rc == -1, rc
         assert needle in _lib.last_error(), _lib.last_error()
 
-    def fwd(q=a, k=a, v=a, o=a, rowstat=a, attn=None, lens=a, B=1, H=2, Tq=5, Tk=5, ldq=768, ldk=768, ldv=768, ldo=256,
-            causal=0, scale=0.1, p=0.0):
-        return lib.ttts_attention_fwd_wide(q, k, v, o, rowstat, attn, lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, scale, p,
-                                           0, None, None)
+    dims = dict(B=1, H=2, Tq=5, Tk=5, ldq=768, ldk=768, ldv=768, ldo=256)
+    grads = dict(lddq=768, lddk=768, lddv=768)
+    tail = dict(causal=0, scale=0.1, p=0.0, seed=0, step_seed=None)
 
-    def bwd(q=a, k=a, v=a, o=a, d_o=a, rowstat=a, delta=a, dq=a, dk=a, dv=a, lens=a, B=1, H=2, Tq=5, Tk=5, ldq=768, ldk=768,
-            ldv=768, ldo=256, lddq=768, lddk=768, lddv=768, causal=0, scale=0.1, p=0.0):
-        return lib.ttts_attention_bwd_wide(q, k, v, o, d_o, rowstat, delta, dq, dk, dv, lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo,
-                                           lddq, lddk, lddv, causal, scale, p, 0, None, None)
+    def caller(fn, order, defaults):
+        def call(**kw):
+            unknown = set(kw) - set(order)
+            assert not unknown, unknown
+            return getattr(lib, fn)(*[kw.get(name, defaults.get(name)) for name in order])
+        return call
 
-    for call, name in ((fwd, "attention_fwd_wide"), (bwd, "attention_bwd_wide")):
-        bad(call(q=None), name + ": null pointer")
-        bad(call(rowstat=None), name + ": null pointer")
-        bad(call(lens=None), name + ": null pointer")
-        bad(call(B=0), "sizes must be positive (B 0,")
-        bad(call(H=-1), "H -1,")
-        bad(call(Tq=0), "Tq 0,")
-        bad(call(Tk=0), "Tk 0)")
-        bad(call(ldq=770), "multiples of 4 floats (ldq 770,")
-        bad(call(ldv=769), "ldv 769,")
-        bad(call(ldo=258), "ldo 258)")
-        bad(call(ldk=128), ">= H*128 = 256 (ldq 768, ldk 128,")
-        bad(call(p=1.0), "dropout p 1 is outside [0, 1)")
-        bad(call(p=-0.25), "dropout p -0.25 is outside [0, 1)")
-        bad(call(p=float("nan")), "is outside [0, 1)")
-        bad(call(causal=1, Tk=6), "causal form needs Tq == Tk (Tq 5, Tk 6)")
-        bad(call(k=a4), "16-byte aligned")
-    bad(fwd(causal=1, attn=a), "non-causal")
-    bad(bwd(dq=None), "null pointer")
-    bad(bwd(lddk=128), "gradient strides must be >= H*128 = 256 (lddq 768, lddk 128,")
-    bad(bwd(d_o=a4), "16-byte aligned")
+    def family(suffix, fwd_extra=(), bwd_extra=(), img=False):
+        scales = ["q_inv", "k_inv", "v_inv"] if img else []
+        fwd = ["q", "k", "v"] + scales + ["o", "stat", "attn", "lens"] + list(dims) + list(tail) + list(fwd_extra) + ["stream"]
+        bwd = (["q", "k", "v"] + scales + ["o", "d_o", "stat", "delta", "dq", "dk", "dv", "lens"] + list(dims) + list(grads) +
+               list(tail) + list(bwd_extra) + ["stream"])
+        ptrs = {n: a for n in ("q", "k", "v", "q_inv", "k_inv", "v_inv", "o", "d_o", "stat", "delta", "dq", "dk", "dv", "lens",
+                               "q_amax", "k_amax", "v_amax", "do_amax")}
+        d = dict(ptrs, **dims, **grads, **tail, q_splits=1, q_inv_rows=0, k_inv_rows=0, stat_plane=0)    # the rest: NULL
+        return caller("ttts_attention_fwd" + suffix, fwd, d), caller("ttts_attention_bwd" + suffix, bwd, d)
+
+    amax3 = ("q_amax", "k_amax", "v_amax")
+    planes = ("q_inv_rows", "k_inv_rows", "stat_plane")
+    # (entry-point suffix, name in the messages, columns per head, the forward requires its statistics output, callers)
+    table = (("_wide", "_wide", 128, True, family("_wide")),
+             ("", "", 64, False, family("")),
+             ("_x6", "", 64, False, family("_x6")),
+             ("_h3", "", 64, False, family("_h3", amax3 + ("o_amax_out", "rowstat_out"),
+                                           ("do_amax", "dq_amax_out", "dkv_amax_out") + amax3 + ("rowstat",))),
+             ("_img", "_img", 64, False, family("_img", ("v_amax", "o_amax_out", "rowstat_out") + planes,
+                                                ("do_amax", "dq_amax_out", "dkv_amax_out", "dkv_partials", "q_splits") + planes,
+                                                img=True)))
+    for suffix, tag, w, fwd_needs_stat, (fwd, bwd) in table:
+        for call, name in ((fwd, "attention_fwd" + tag), (bwd, "attention_bwd" + tag)):
+            bad(call(q=None), name + ": null pointer")
+            if fwd_needs_stat or call is bwd:
+                bad(call(stat=None), name + ": null pointer")
+            bad(call(lens=None), name + ": null pointer")
+            bad(call(B=0), "sizes must be positive (B 0,")
+            bad(call(H=-1), "H -1,")
+            bad(call(Tq=0), "Tq 0,")
+            bad(call(Tk=0), "Tk 0)")
+            bad(call(ldq=770), "multiples of 4 floats (ldq 770,")
+            bad(call(ldv=769), "ldv 769,")
+            bad(call(ldo=258), "ldo 258)")
+            bad(call(ldk=w), f">= H*{w} = {2 * w} (ldq 768, ldk {w},")
+            bad(call(p=1.0), "dropout p 1 is outside [0, 1)")
+            bad(call(p=-0.25), "dropout p -0.25 is outside [0, 1)")
+            bad(call(p=float("nan")), "is outside [0, 1)")
+            bad(call(causal=1, Tk=6), "causal form needs Tq == Tk (Tq 5, Tk 6)")
+            bad(call(k=a4), "16-byte aligned")
+            assert name + ":" in _lib.last_error(), (suffix, _lib.last_error())
+        bad(fwd(causal=1, attn=a), "non-causal")
+        bad(bwd(dq=None), "null pointer")
+        bad(bwd(lddk=w), f"gradient strides must be >= H*{w} = {2 * w} (lddq 768, lddk {w},")
+        bad(bwd(d_o=a4), "16-byte aligned")
+    fwd = table[0][4][0]
+    # the head-image entry points keep their own checks on top
+    img_fwd, img_bwd = table[4][4]
+    bad(img_fwd(v_amax=None), "attention_fwd_img: null pointer")
+    bad(img_bwd(do_amax=None), "attention_bwd_img: null pointer")
+    bad(img_fwd(B=4, Tq=300, Tk=300, q_inv_rows=1199), "plane strides smaller than the batch")
+    bad(img_bwd(stat_plane=9), "plane strides smaller than the batch")
+    bad(img_fwd(Tq=1 << 20, ldq=1024), "exceeds 4 GiB")
+    bad(img_bwd(Tq=1 << 20, ldo=1024), "d_o exceeds 4 GiB")
+    bad(img_bwd(q_splits=17), "q_splits out of 1..16")
+    bad(img_bwd(q_splits=2), "query splits need a workspace")
+    # ... and the fp16x3 ones the partial maxima of their operands
+    bad(table[3][4][0](q_amax=None), "q_amax / k_amax / v_amax are required")
+    bad(table[3][4][1](do_amax=None), "do_amax, q_amax, k_amax and v_amax")
 
     # ttts_heads_pad_w(src, ld_src, dst, rows, H, head_dim, width, stream) / ttts_heads_unpad_w(src, dst, ld_dst, rows, H, ...)
     bad(lib.ttts_heads_pad_w(a, 192, a, 4, 2, 96, 96, None), "width 96 must be 64 or 128")

@@ -27,32 +27,6 @@ namespace ttts {
 #define TTTS_FWD_W 3
 #endif
 
-// ---- cooperative staging (256 threads): KB rows x 64 floats from global straight into LDS; rows beyond
-// `nrows_total` are zero.  No register prefetch across the compute phase: with 3-4 workgroups per CU the other
-// workgroups cover the load latency, and the registers are worth more as occupancy.
-template <bool PADDED>
-__device__ __forceinline__ void stage_rows(const float* base, long row0, long nrows_total, int ld, int tid, float* dst,
-                                           float scale) {
-    constexpr int LDD = PADDED ? KT_LD : HD;
-    const RowSrc src = row_src(base, nrows_total, ld);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int row = (tid >> 4) + 16 * i, c4 = tid & 15;
-        long gr = row0 + row;
-        v[i] = row_load4(src, gr, c4);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int row = (tid >> 4) + 16 * i, c4 = tid & 15;
-        float* d = dst + row * LDD + c4 * 4;
-        if (PADDED) {
-            d[0] = v[i].x * scale; d[1] = v[i].y * scale; d[2] = v[i].z * scale; d[3] = v[i].w * scale;
-        } else {
-            *reinterpret_cast<float4*>(d) = make_float4(v[i].x * scale, v[i].y * scale, v[i].z * scale, v[i].w * scale);
-        }
-    }
-}
 // =====================================================================================  forward
 template <bool CAUSAL, bool WRITE_A>
 __global__ __launch_bounds__(256, TTTS_FWD_W) void attn_fwd_kernel(AttnArgs a) {
@@ -74,15 +48,8 @@ __global__ __launch_bounds__(256, TTTS_FWD_W) void attn_fwd_kernel(AttnArgs a) {
     const int qg = qw0 + l31;
     float* scratch = smem + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst_live = (kend + KB - 1) / KB;
-    const int nst = WRITE_A ? (a.Tk + KB - 1) / KB : nst_live;
-    int wave_kend = WRITE_A ? a.Tk : kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, WRITE_A, KB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -112,27 +79,19 @@ __global__ __launch_bounds__(256, TTTS_FWD_W) void attn_fwd_kernel(AttnArgs a) {
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf, qreg[j], s, 0, 0, 0);
         }
     };
-    auto alive = [&](int key_g) -> bool { return key_g < klen && (!CAUSAL || key_g <= qg); };
-    // dropout on the 16 weights of this lane: keys (r, r+1) with r even are neighbours and share one hash
-    auto drop16 = [&](float (&p)[16], int key0) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {     // registers r .. r+3 are four neighbouring keys: one hash
-            const uint32_t qh = attn_quad_hash(seed_eff, rowid, (uint32_t)(key0 + acc_row(r, half)) >> 2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) p[r + e] = attn_keep_word(qh, attn_drop_mult(e), thr16) ? p[r + e] * a.drop_scale : 0.f;
-        }
-    };
+    auto alive = [&](int key_g) -> bool { return attn_alive<CAUSAL>(key_g, klen, qg); };
+    auto drop16 = [&](float (&p)[16], int key0) { attn_drop16<true>(p, seed_eff, rowid, key0, half, thr16, a.drop_scale); };
 
     if (WRITE_A) {
         // ---------------- pass 1: row max / row sum only
-        for (int t = 0; t < nst_live; ++t) {
+        for (int t = 0; t < kr.nst_live; ++t) {
             __syncthreads();
-            stage_rows<true>(kb_, (long)t * KB, a.Tk, a.ldk, tid, Ks, 1.f);
+            stage_rows<HD, true>(kb_, (long)t * KB, a.Tk, a.ldk, tid, Ks, 1.f);
             __syncthreads();
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 const int key0 = t * KB + sub * 32;
-                if (key0 >= kend) break;
+                if (key0 >= kr.kend) break;
                 f32x16 s;
                 scores(Ks + sub * 32 * KT_LD, s);
                 float mx = NEG_INF;
@@ -159,15 +118,15 @@ __global__ __launch_bounds__(256, TTTS_FWD_W) void attn_fwd_kernel(AttnArgs a) {
     const float inv_l = (l > 0.f) ? 1.f / l : 0.f;
 
     // ---------------- main pass
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
-        stage_rows<true>(kb_, (long)t * KB, a.Tk, a.ldk, tid, Ks, 1.f);
-        stage_rows<false>(vb_, (long)t * KB, a.Tk, a.ldv, tid, Vs, 1.f);
+        stage_rows<HD, true>(kb_, (long)t * KB, a.Tk, a.ldk, tid, Ks, 1.f);
+        stage_rows<HD, false>(vb_, (long)t * KB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int key0 = t * KB + sub * 32;
-            if (key0 >= wave_kend) break;      // sub-tile entirely above this wave's causal frontier / past the keys
+            if (key0 >= kr.wave_kend) break;      // sub-tile entirely above this wave's causal frontier / past the keys
             const float* ks = Ks + sub * 32 * KT_LD;
             const float* vs = Vs + sub * 32 * HD;
             f32x16 s;
@@ -255,14 +214,8 @@ __global__ __launch_bounds__(256, TTTS_DQ_W) void attn_bwd_dq_kernel(AttnArgs a)
     const int qg = qw0 + l31;
     float* scratch = smem + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst = (kend + KB - 1) / KB;
-    int wave_kend = kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, false, KB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -296,15 +249,15 @@ __global__ __launch_bounds__(256, TTTS_DQ_W) void attn_bwd_dq_kernel(AttnArgs a)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dq[0][r] = 0.f; dq[1][r] = 0.f; }
 
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
-        stage_rows<true>(kb_, (long)t * KB, a.Tk, a.ldk, tid, Ks, 1.f);
-        stage_rows<true>(vb_, (long)t * KB, a.Tk, a.ldv, tid, Vs, 1.f);
+        stage_rows<HD, true>(kb_, (long)t * KB, a.Tk, a.ldk, tid, Ks, 1.f);
+        stage_rows<HD, true>(vb_, (long)t * KB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int key0 = t * KB + sub * 32;
-            if (key0 >= wave_kend) break;
+            if (key0 >= kr.wave_kend) break;
             const float* ks = Ks + sub * 32 * KT_LD;
             const float* vs = Vs + sub * 32 * KT_LD;
             f32x16 s, dp;
@@ -326,10 +279,9 @@ __global__ __launch_bounds__(256, TTTS_DQ_W) void attn_bwd_dq_kernel(AttnArgs a)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int kg = key_g + e;
-                    bool live = kg < klen && (!CAUSAL || kg <= qg);
-                    float p = live ? __expf(s[r + e] - lse_q) : 0.f;
+                    float p = attn_alive<CAUSAL>(kg, klen, qg) ? __expf(s[r + e] - lse_q) : 0.f;
                     float g = dp[r + e];
-                    if (a.thr != 0u) g = attn_keep_word(qh, attn_drop_mult(e), thr16) ? g * a.drop_scale : 0.f;
+                    if (a.thr != 0u) g = attn_drop1<true>(g, qh, e, thr16, a.drop_scale);
                     ds[r + e] = p * (g - delta);
                 }
             }
@@ -365,9 +317,7 @@ __global__ __launch_bounds__(256, TTTS_DKV_W) void attn_bwd_dkv_kernel(AttnArgs 
     const int kg = kw0 + l31;
     float* scratch = smem + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -391,13 +341,12 @@ __global__ __launch_bounds__(256, TTTS_DKV_W) void attn_bwd_dkv_kernel(AttnArgs 
     for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f; }
 
     const int nqs = (a.Tq + KB - 1) / KB;
-    int qs_begin = CAUSAL ? (k0 / KB) : 0;        // queries below the block's first key never see it
-    if (k0 >= klen) qs_begin = nqs;               // whole key block is padding: gradients are zero
+    const int qs_begin = attn_qs_begin<CAUSAL, KB>(k0, klen, nqs);
 
     for (int qs = qs_begin; qs < nqs; ++qs) {
         __syncthreads();
-        stage_rows<true>(qb_, (long)qs * KB, a.Tq, a.ldq, tid, Qs, a.qscale);
-        stage_rows<true>(gb_, (long)qs * KB, a.Tq, a.ldo, tid, Gs, 1.f);
+        stage_rows<HD, true>(qb_, (long)qs * KB, a.Tq, a.ldq, tid, Qs, a.qscale);
+        stage_rows<HD, true>(gb_, (long)qs * KB, a.Tq, a.ldo, tid, Gs, 1.f);
         if (tid < KB) {
             int q = qs * KB + tid;
             lse_s[tid] = (q < a.Tq) ? a.lse[arow + q] : 0.f;
@@ -426,7 +375,7 @@ __global__ __launch_bounds__(256, TTTS_DKV_W) void attn_bwd_dkv_kernel(AttnArgs 
             for (int r = 0; r < 16; ++r) {
                 const int qrow = acc_row(r, half);
                 const int q_g = qt0 + qrow;
-                bool live = kg < klen && (!CAUSAL || kg <= q_g) && q_g < a.Tq;
+                bool live = attn_alive<CAUSAL>(kg, klen, q_g) && q_g < a.Tq;
                 float p = live ? __expf(s[r] - lse_s[sub * 32 + qrow]) : 0.f;
                 float g = dp[r];
                 float pk = p;
@@ -565,15 +514,8 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDX_W) void attn_fwd_x6_ke
     const int qg = qw0 + l31;
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst_live = (kend + KB - 1) / KB;
-    const int nst = WRITE_A ? (a.Tk + KB - 1) / KB : nst_live;
-    int wave_kend = WRITE_A ? a.Tk : kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, WRITE_A, KB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -611,26 +553,19 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDX_W) void attn_fwd_x6_ke
             mfma_x6(s, kf, qf[st]);
         }
     };
-    auto alive = [&](int key_g) -> bool { return key_g < klen && (!CAUSAL || key_g <= qg); };
-    auto drop16 = [&](float (&p)[16], int key0) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {     // registers r .. r+3 are four neighbouring keys: one hash
-            const uint32_t qh = attn_quad_hash(seed_eff, rowid, (uint32_t)(key0 + acc_row(r, half)) >> 2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) p[r + e] = attn_keep_word(qh, attn_drop_mult(e), thr16) ? p[r + e] * a.drop_scale : 0.f;
-        }
-    };
+    auto alive = [&](int key_g) -> bool { return attn_alive<CAUSAL>(key_g, klen, qg); };
+    auto drop16 = [&](float (&p)[16], int key0) { attn_drop16<true>(p, seed_eff, rowid, key0, half, thr16, a.drop_scale); };
 
     if (WRITE_A) {
         // ---------------- pass 1: row max / row sum only
-        for (int t = 0; t < nst_live; ++t) {
+        for (int t = 0; t < kr.nst_live; ++t) {
             __syncthreads();
             stage_split_rows(kb_, (long)t * KB, a.Tk, a.ldk, tid, Kp);
             __syncthreads();
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 const int key0 = t * KB + sub * 32;
-                if (key0 >= kend) break;
+                if (key0 >= kr.kend) break;
                 f32x16 s;
                 scores(sub, s);
                 float mx = NEG_INF;
@@ -657,7 +592,7 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDX_W) void attn_fwd_x6_ke
     const float inv_l = (l > 0.f) ? 1.f / l : 0.f;
 
     // ---------------- main pass
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
         stage_split_rows(kb_, (long)t * KB, a.Tk, a.ldk, tid, Kp);
         stage_split_cols(vb_, (long)t * KB, a.Tk, a.ldv, tid, Vt);
@@ -665,7 +600,7 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDX_W) void attn_fwd_x6_ke
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int key0 = t * KB + sub * 32;
-            if (key0 >= wave_kend) break;
+            if (key0 >= kr.wave_kend) break;
             f32x16 s;
             scores(sub, s);
             float p[16];
@@ -877,15 +812,8 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDH_W) void attn_fwd_h3_ke
     const int qg = qw0 + l31;
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst_live = (kend + KB - 1) / KB;
-    const int nst = WRITE_A ? (a.Tk + KB - 1) / KB : nst_live;
-    int wave_kend = WRITE_A ? a.Tk : kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, WRITE_A, KB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -925,30 +853,19 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDH_W) void attn_fwd_h3_ke
             mfma_h3(s, kf, qf[st]);
         }
     };
-    auto alive = [&](int key_g) -> bool { return key_g < klen && (!CAUSAL || key_g <= qg); };
-    auto drop16 = [&](float (&p)[16], int key0) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {     // registers r .. r+3 are four neighbouring keys: one hash
-            const uint32_t qh = attn_quad_hash(seed_eff, rowid, (uint32_t)(key0 + acc_row(r, half)) >> 2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // (the 1/(1-p) of the kept weights rides in the final output scale unless the weights themselves are returned)
-                const bool keep = attn_keep_word(qh, attn_drop_mult(e), thr16);
-                p[r + e] = keep ? (WRITE_A ? p[r + e] * a.drop_scale : p[r + e]) : 0.f;
-            }
-        }
-    };
+    auto alive = [&](int key_g) -> bool { return attn_alive<CAUSAL>(key_g, klen, qg); };
+    auto drop16 = [&](float (&p)[16], int key0) { attn_drop16<WRITE_A>(p, seed_eff, rowid, key0, half, thr16, a.drop_scale); };
 
     if (WRITE_A) {
         // ---------------- pass 1: row max / row sum only
-        for (int t = 0; t < nst_live; ++t) {
+        for (int t = 0; t < kr.nst_live; ++t) {
             __syncthreads();
             stage_split_rows_h3(kb_, (long)t * KB, a.Tk, a.ldk, tid, Kp, hs.sk);
             __syncthreads();
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 const int key0 = t * KB + sub * 32;
-                if (key0 >= kend) break;
+                if (key0 >= kr.kend) break;
                 f32x16 s;
                 scores(sub, s);
                 float mx = NEG_INF;
@@ -981,7 +898,7 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDH_W) void attn_fwd_h3_ke
     float mcs_last = 0.f;        // online form: the subtrahend of the last tile (= of the final maximum)
 
     // ---------------- main pass
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
         stage_split_rows_h3(kb_, (long)t * KB, a.Tk, a.ldk, tid, Kp, hs.sk);
         stage_split_cols_h3(vb_, (long)t * KB, a.Tk, a.ldv, tid, Vt, hs.sv);
@@ -989,7 +906,7 @@ __global__ __launch_bounds__(256, WRITE_A ? 2 : TTTS_FWDH_W) void attn_fwd_h3_ke
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int key0 = t * KB + sub * 32;
-            if (key0 >= wave_kend) break;
+            if (key0 >= kr.wave_kend) break;
             f32x16 s;
             scores(sub, s);
             float p[16];
@@ -1194,14 +1111,8 @@ __global__ __launch_bounds__(256, TTTS_DQX_W) void attn_bwd_dq_x6_kernel(AttnArg
     const int qg = qw0 + l31;
     float* scratch = reinterpret_cast<float*>(xsd) + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst = (kend + KB - 1) / KB;
-    int wave_kend = kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, false, KB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -1238,7 +1149,7 @@ __global__ __launch_bounds__(256, TTTS_DQX_W) void attn_bwd_dq_x6_kernel(AttnArg
 
     const int rq = tid >> 4, dqd = tid & 15;
     const int kpos = (rq >> 3) * 32 + perm_pos(rq);
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
         {
             float4 v[4];
@@ -1251,7 +1162,7 @@ __global__ __launch_bounds__(256, TTTS_DQX_W) void attn_bwd_dq_x6_kernel(AttnArg
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int key0 = t * KB + sub * 32;
-            if (key0 >= wave_kend) break;
+            if (key0 >= kr.wave_kend) break;
             f32x16 s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
@@ -1283,9 +1194,9 @@ __global__ __launch_bounds__(256, TTTS_DQX_W) void attn_bwd_dq_x6_kernel(AttnArg
                 for (int e = 0; e < 4; ++e) {
                     const int kg = key_g + e;
                     float p = __expf(s[r + e] - lse_q);
-                    if (!full) p = (kg < klen && (!CAUSAL || kg <= qg)) ? p : 0.f;
+                    if (!full) p = attn_alive<CAUSAL>(kg, klen, qg) ? p : 0.f;
                     float g = dp[r + e];
-                    if (a.thr != 0u) g = attn_keep_word(qh, attn_drop_mult(e), thr16) ? g * a.drop_scale : 0.f;
+                    if (a.thr != 0u) g = attn_drop1<true>(g, qh, e, thr16, a.drop_scale);
                     ds[r + e] = p * (g - delta);
                 }
             }
@@ -1367,9 +1278,7 @@ __global__ __launch_bounds__(256, TTTS_DKVX_W) void attn_bwd_dkv_x6_kernel(AttnA
     const uint32_t key_mult = attn_drop_mult((uint32_t)kg);
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -1391,8 +1300,7 @@ __global__ __launch_bounds__(256, TTTS_DKVX_W) void attn_bwd_dkv_x6_kernel(AttnA
     for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f; }
 
     const int nqs = (a.Tq + QS - 1) / QS;
-    int qs_begin = CAUSAL ? (k0 / QS) : 0;
-    if (k0 >= klen) qs_begin = nqs;
+    const int qs_begin = attn_qs_begin<CAUSAL, QS>(k0, klen, nqs);
 
     // staging roles: threads 0..127 take Q, 128..255 take dO; each a 4 x 4 patch of the 32 x 64 stage
     const int st_t = tid & 127, rq = st_t >> 4, dqd = st_t & 15;
@@ -1609,14 +1517,8 @@ __global__ __launch_bounds__(256, TTTS_DQH_W) void attn_bwd_dq_h3_kernel(AttnArg
     const int qg = qw0 + l31;
     float* scratch = reinterpret_cast<float*>(xsd) + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst = (kend + KB - 1) / KB;
-    int wave_kend = kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, false, KB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -1677,7 +1579,7 @@ __global__ __launch_bounds__(256, TTTS_DQH_W) void attn_bwd_dq_h3_kernel(AttnArg
 
     const int rq = tid >> 4, dqd = tid & 15;
     const int kpos = (rq >> 3) * 32 + perm_pos(rq);
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
         {
             float4 v[4];
@@ -1690,7 +1592,7 @@ __global__ __launch_bounds__(256, TTTS_DQH_W) void attn_bwd_dq_h3_kernel(AttnArg
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int key0 = t * KB + sub * 32;
-            if (key0 >= wave_kend) break;
+            if (key0 >= kr.wave_kend) break;
             f32x16 s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
@@ -1722,9 +1624,9 @@ __global__ __launch_bounds__(256, TTTS_DQH_W) void attn_bwd_dq_h3_kernel(AttnArg
                 for (int e = 0; e < 4; ++e) {
                     const int kg = key_g + e;
                     float p = fast_exp2(__builtin_fmaf(s[r + e], H3A_C2, -m_q) - l2_q);
-                    if (!full) p = (kg < klen && (!CAUSAL || kg <= qg)) ? p : 0.f;
+                    if (!full) p = attn_alive<CAUSAL>(kg, klen, qg) ? p : 0.f;
                     float g = dp[r + e] * dp_unscale;
-                    if (a.thr != 0u) g = attn_keep_word(qh, attn_drop_mult(e), thr16) ? g : 0.f;
+                    if (a.thr != 0u) g = attn_drop1<false>(g, qh, e, thr16, a.drop_scale);
                     ds[r + e] = saturated ? 0.f : p * (g - delta);
                 }
             }
@@ -1788,9 +1690,7 @@ __global__ __launch_bounds__(256, TTTS_DKVH_W) void attn_bwd_dkv_h3_kernel(AttnA
     const uint32_t key_mult = attn_drop_mult((uint32_t)kg);
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * KT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * HD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * HD;
@@ -1817,8 +1717,7 @@ __global__ __launch_bounds__(256, TTTS_DKVH_W) void attn_bwd_dkv_h3_kernel(AttnA
     const float dp_unscale = inv_g * hs.inv_sv * a.drop_scale;  // ... times the 1/(1-p) of kept weights (1 without dropout)
     float sds = 0.f;                        // this key's dS pre-scale (power of two), see attn_bwd_dq_h3_kernel
     const int nqs = (a.Tq + QS - 1) / QS;
-    int qs_begin = CAUSAL ? (k0 / QS) : 0;
-    if (k0 >= klen) qs_begin = nqs;
+    const int qs_begin = attn_qs_begin<CAUSAL, QS>(k0, klen, nqs);
 
     // staging roles: threads 0..127 take Q, 128..255 take dO; each a 4 x 4 patch of the 32 x 64 stage
     const int st_t = tid & 127, rq = st_t >> 4, dqd = st_t & 15;
@@ -1998,62 +1897,9 @@ __global__ __launch_bounds__(256, TTTS_DKVH_W) void attn_bwd_dkv_h3_kernel(AttnA
     wave_store_rows(dv, scratch, a.dv + (long)b * a.Tk * a.lddv + h * HD, kw0, a.Tk, a.lddv, lane, 1.f);
 }
 
-static int check_common(const char* name, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, float drop_p) {
-    TTTS_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "%s: bad dims", name);
-    TTTS_REQUIRE((long)B * H < (1L << 31) && cdiv(Tq, QB) <= 65535 && cdiv(Tk, QB) <= 65535, "%s: grid too large", name);
-    TTTS_REQUIRE(ldq >= H * HD && ldk >= H * HD && ldv >= H * HD && ldo >= H * HD, "%s: row strides must be >= H*64", name);
-    TTTS_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0, "%s: row strides must be multiples of 4", name);
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: bad dropout p", name);
-    return TTTS_OK;
-}
-
 }  // namespace ttts
 
 using namespace ttts;
-
-template <bool CAUSAL>
-static int launch_bwd_x6(const AttnArgs& a, dim3 gq, dim3 gk, hipStream_t stream) {
-    static bool configured = false;   // more than 64 KB of LDS per workgroup needs an explicit opt-in, once per kernel
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_x6_kernel<CAUSAL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, DQX_SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_x6_kernel<CAUSAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, DKVX_SMEM);
-        if (e != hipSuccess) {
-            set_error("attention_bwd: cannot reserve %d bytes of LDS: %s", DQX_SMEM, hipGetErrorString(e));
-            return TTTS_ERR_LAUNCH;
-        }
-        configured = true;
-    }
-    hipLaunchKernelGGL((attn_bwd_dq_x6_kernel<CAUSAL>), gq, dim3(256), DQX_SMEM, stream, a);
-    TTTS_LAUNCH_CHECK("attn_bwd_dq_x6_kernel");
-    hipLaunchKernelGGL((attn_bwd_dkv_x6_kernel<CAUSAL>), gk, dim3(256), DKVX_SMEM, stream, a);
-    TTTS_LAUNCH_CHECK("attn_bwd_dkv_x6_kernel");
-    return TTTS_OK;
-}
-
-template <bool CAUSAL>
-static int launch_bwd_h3(const AttnArgs& a, dim3 gq, dim3 gk, hipStream_t stream) {
-    static bool configured = false;   // dynamic LDS sizes are registered once per kernel
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_h3_kernel<CAUSAL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, DQH_SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_h3_kernel<CAUSAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, DKVH_SMEM);
-        if (e != hipSuccess) {
-            set_error("attention_bwd_h3: cannot reserve %d bytes of LDS: %s", DKVH_SMEM, hipGetErrorString(e));
-            return TTTS_ERR_LAUNCH;
-        }
-        configured = true;
-    }
-    hipLaunchKernelGGL((attn_bwd_dq_h3_kernel<CAUSAL>), gq, dim3(256), DQH_SMEM, stream, a);
-    TTTS_LAUNCH_CHECK("attn_bwd_dq_h3_kernel");
-    hipLaunchKernelGGL((attn_bwd_dkv_h3_kernel<CAUSAL>), gk, dim3(256), DKVH_SMEM, stream, a);
-    TTTS_LAUNCH_CHECK("attn_bwd_dkv_h3_kernel");
-    return TTTS_OK;
-}
 
 extern "C" {
 
@@ -2066,48 +1912,18 @@ static int attention_fwd_impl(const float* q, const float* k, const float* v, fl
     hipStream_t stream = (hipStream_t)stream_;
     TTTS_REQUIRE(q && k && v && o && key_lens, "attention_fwd: null pointer");
     TTTS_REQUIRE(form != 2 || (q_amax && k_amax && v_amax), "attention_fwd_h3: q_amax / k_amax / v_amax are required");
-    int rc = check_common("attention_fwd", B, H, Tq, Tk, ldq, ldk, ldv, ldo, drop_p);
+    int rc = attn_check("attention_fwd", HD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
     if (rc) return rc;
     TTTS_REQUIRE(!(causal && attn), "attention_fwd: weights output is only provided for the non-causal (cross) form");
-    TTTS_REQUIRE(!causal || Tq == Tk, "attention_fwd: causal form needs Tq == Tk");
     TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "attention_fwd: q/k/v must be 16-byte aligned");
     AttnArgs a = {};
-    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.attn = attn; a.key_lens = key_lens;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.thr = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
-    a.drop_scale = 1.f / (1.f - drop_p);
-    a.qscale = q_scale;
-    a.seed = seed; a.step_seed = step_seed;
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.attn = attn;
     a.q_amax = q_amax; a.k_amax = k_amax; a.v_amax = v_amax; a.o_amax = o_amax_out; a.rowstat = rowstat_out;
-    dim3 grid(B * H, cdiv(Tq, QB), 1);
-    if (form == 2) {
-        if (causal)
-            hipLaunchKernelGGL((attn_fwd_h3_kernel<true, false>), grid, dim3(256), 0, stream, a);
-        else if (attn)
-            hipLaunchKernelGGL((attn_fwd_h3_kernel<false, true>), grid, dim3(256), 0, stream, a);
-        else
-            hipLaunchKernelGGL((attn_fwd_h3_kernel<false, false>), grid, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_fwd_h3_kernel");
-        return TTTS_OK;
-    }
-    if (form == 1) {
-        if (causal)
-            hipLaunchKernelGGL((attn_fwd_x6_kernel<true, false>), grid, dim3(256), 0, stream, a);
-        else if (attn)
-            hipLaunchKernelGGL((attn_fwd_x6_kernel<false, true>), grid, dim3(256), 0, stream, a);
-        else
-            hipLaunchKernelGGL((attn_fwd_x6_kernel<false, false>), grid, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_fwd_x6_kernel");
-        return TTTS_OK;
-    }
-    if (causal)
-        hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(256), 0, stream, a);
-    else if (attn)
-        hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(256), 0, stream, a);
-    TTTS_LAUNCH_CHECK("attn_fwd_kernel");
-    return TTTS_OK;
+    const bool weights = attn != nullptr;
+    if (form == 2) return attn_launch_fwd("attn_fwd_h3_kernel", ATTN_FWD_FORMS(attn_fwd_h3_kernel), causal, weights, a, stream);
+    if (form == 1) return attn_launch_fwd("attn_fwd_x6_kernel", ATTN_FWD_FORMS(attn_fwd_x6_kernel), causal, weights, a, stream);
+    return attn_launch_fwd("attn_fwd_kernel", ATTN_FWD_FORMS(attn_fwd_kernel), causal, weights, a, stream);
 }
 
 int ttts_attention_fwd(const float* q, const float* k, const float* v, float* o, float* lse, float* attn,
@@ -2142,41 +1958,29 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, co
     TTTS_REQUIRE(q && k && v && o && do_ && lse && delta && dq && dk && dv && key_lens, "attention_bwd: null pointer");
     TTTS_REQUIRE(form != 2 || (do_amax && q_amax && k_amax && v_amax),
                  "attention_bwd_h3: do_amax, q_amax, k_amax and v_amax (partial maxima of the operands) are required");
-    int rc = check_common("attention_bwd", B, H, Tq, Tk, ldq, ldk, ldv, ldo, drop_p);
+    int rc = attn_check("attention_bwd", HD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = attn_check_grad_strides("attention_bwd", HD, H, lddq, lddk, lddv);
     if (rc) return rc;
-    TTTS_REQUIRE(lddq >= H * HD && lddk >= H * HD && lddv >= H * HD, "attention_bwd: gradient strides must be >= H*64");
-    TTTS_REQUIRE(!causal || Tq == Tk, "attention_bwd: causal form needs Tq == Tk");
     TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)do_) & 15) == 0,
                  "attention_bwd: q/k/v/o/do must be 16-byte aligned");
     AttnArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
     a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = do_; a.lse = const_cast<float*>(lse);
-    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv; a.key_lens = key_lens;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
     a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.thr = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
-    a.drop_scale = 1.f / (1.f - drop_p);
-    a.qscale = q_scale;
-    a.seed = seed; a.step_seed = step_seed;
-    dim3 gq(B * H, cdiv(Tq, QB), 1), gk(B * H, cdiv(Tk, QB), 1);
     if (form == 2) {
         a.do_amax = do_amax; a.do_amax_n = TTTS_AMAX_SLOTS;
         a.amax_dq = dq_amax_out; a.amax_dkv = dkv_amax_out;
         a.q_amax = q_amax; a.k_amax = k_amax; a.v_amax = v_amax;
         a.rowstat = const_cast<float*>(rowstat);
-        return causal ? launch_bwd_h3<true>(a, gq, gk, stream) : launch_bwd_h3<false>(a, gq, gk, stream);
+        return ATTN_LAUNCH_BWD(attn_bwd_dq_h3_kernel, DQH_SMEM, attn_bwd_dkv_h3_kernel, DKVH_SMEM, causal, "attention_bwd_h3",
+                               "attn_bwd_dq_h3_kernel", "attn_bwd_dkv_h3_kernel", a, 1, stream);
     }
-    if (form == 1) return causal ? launch_bwd_x6<true>(a, gq, gk, stream) : launch_bwd_x6<false>(a, gq, gk, stream);
-    if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), gq, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_bwd_dq_kernel");
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true>), gk, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<false>), gq, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_bwd_dq_kernel");
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<false>), gk, dim3(256), 0, stream, a);
-    }
-    TTTS_LAUNCH_CHECK("attn_bwd_dkv_kernel");
-    return TTTS_OK;
+    if (form == 1)
+        return ATTN_LAUNCH_BWD(attn_bwd_dq_x6_kernel, DQX_SMEM, attn_bwd_dkv_x6_kernel, DKVX_SMEM, causal, "attention_bwd",
+                               "attn_bwd_dq_x6_kernel", "attn_bwd_dkv_x6_kernel", a, 1, stream);
+    return ATTN_LAUNCH_BWD(attn_bwd_dq_kernel, 0, attn_bwd_dkv_kernel, 0, causal, "attention_bwd", "attn_bwd_dq_kernel",
+                           "attn_bwd_dkv_kernel", a, 1, stream);
 }
 
 int ttts_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* do_,

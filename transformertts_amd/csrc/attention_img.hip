@@ -180,15 +180,9 @@ __global__ __launch_bounds__(256, KT == 32 ? 3 : 2) void attn_fwd_img_kernel(Att
     const int qg = qw0 + l31;
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * OUT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst_live = (kend + KT - 1) / KT;
-    const int nst = WRITE_A ? (a.Tk + KT - 1) / KT : nst_live;
-    int wave_kend = WRITE_A ? a.Tk : kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, WRITE_A, KT>(klen, a.Tk, q0, qw0);
+    const int kend = kr.kend, nst_live = kr.nst_live, nst = kr.nst, wave_kend = kr.wave_kend;
 
     float Ev, inv_Ev;
     img_tensor_scale(a.v_amax, lane, wave, red4, Ev, inv_Ev);
@@ -286,17 +280,7 @@ __global__ __launch_bounds__(256, KT == 32 ? 3 : 2) void attn_fwd_img_kernel(Att
         }
     };
     auto alive = [&](int key_g) -> bool { return key_g < klen && (!CAUSAL || key_g <= qg); };
-    auto drop16 = [&](float (&p)[16], int key0) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {     // registers r .. r+3 are four neighbouring keys: one hash
-            const uint32_t qh = attn_quad_hash(seed_eff, rowid, (uint32_t)(key0 + acc_row(r, half)) >> 2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const bool keep = attn_keep_word(qh, attn_drop_mult(e), thr16);
-                p[r + e] = keep ? (WRITE_A ? p[r + e] * a.drop_scale : p[r + e]) : 0.f;
-            }
-        }
-    };
+    auto drop16 = [&](float (&p)[16], int key0) { attn_drop16<WRITE_A>(p, seed_eff, rowid, key0, half, thr16, a.drop_scale); };
 
     if (WRITE_A) {
         // ---------------- pass 1: row max / row sum only (K tiles alone)
@@ -507,9 +491,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_img_maps_kernel(AttnImgArgs a
     const int qg = qw0 + l31;
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * OUT_LD;
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
     const int nsub = (a.Tk + 31) / 32;                 // <= 4 (the launcher checks Tk <= 128)
 
     float Ev, inv_Ev;
@@ -768,14 +750,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_img_kernel(AttnImgArgs a) 
     float* scratch = reinterpret_cast<float*>(xs) + wave * 32 * KT_LD;
     float* scratch4 = reinterpret_cast<float*>(xs) + wave * 32 * OUT_LD;     // the epilogue's (16-byte rows)
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst = (kend + KB - 1) / KB;
-    int wave_kend = kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, false, KB>(klen, a.Tk, q0, qw0);
+    const int nst = kr.nst, wave_kend = kr.wave_kend;
 
     const float* ob_ = a.o + (long)b * a.Tq * a.ldo + h * HD;
     const float* gb_ = a.dout + (long)b * a.Tq * a.ldo + h * HD;
@@ -933,7 +910,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_img_kernel(AttnImgArgs a) 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float g = dp[r + e] * (viv[r + e] * dp_unscale);
-                    g = attn_keep_word(qh, attn_drop_mult(e), thr16) ? g : 0.f;
+                    g = attn_drop1<false>(g, qh, e, thr16, a.drop_scale);
                     // dS carries the key's 2^-e_k from here on: the K'^T it meets below is K 2^e_k
                     ds[r + e] = pw[r + e] * (g - delta) * kiv[r + e];
                 }
@@ -999,9 +976,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_img_kernel(AttnImgArgs a)
     const uint32_t key_mult = attn_drop_mult((uint32_t)kg);
     float* scratch4 = reinterpret_cast<float*>(xs) + wave * 32 * OUT_LD;     // the epilogue's scratch (aliases the stages)
 
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
     const long arow = ((long)(b * a.H + h) * a.Tq);
 
     float s_g, inv_g;
@@ -1034,8 +1009,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_img_kernel(AttnImgArgs a)
     const int nqs_all = (a.Tq + DKI_QS - 1) / DKI_QS;
     const int per_z = (nqs_all + (int)gridDim.z - 1) / (int)gridDim.z;
     const int nqs = min(nqs_all, ((int)blockIdx.z + 1) * per_z);
-    int qs_begin = max(CAUSAL ? (k0 / DKI_QS) : 0, (int)blockIdx.z * per_z);
-    if (k0 >= klen || qs_begin > nqs) qs_begin = nqs;
+    int qs_begin = max(attn_qs_begin<CAUSAL, DKI_QS>(k0, klen, nqs), (int)blockIdx.z * per_z);
+    if (qs_begin > nqs) qs_begin = nqs;
 
     // ---- the ring.  This wave moves rows 8 w .. 8 w + 7 of a stage: one 1-KB piece per Q plane (source chunks swizzled) and two
     // raw pieces of dO; waves 0 / 1 also the row statistics.  Rows past Tq are clamped (finite data; masked below).
@@ -1155,7 +1130,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_img_kernel(AttnImgArgs a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int q_g = qt0 + acc_row(r, half);
-                    pd[r] = (kg < klen && (!CAUSAL || kg <= q_g) && q_g < a.Tq) ? pd[r] : 0.f;
+                    pd[r] = (attn_alive<CAUSAL>(kg, klen, q_g) && q_g < a.Tq) ? pd[r] : 0.f;
                 }
             }
 #pragma unroll
@@ -1278,14 +1253,19 @@ __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(const float* __res
 #define TTTS_AIMG_KT 32
 #endif
 
-static int check_img(const char* name, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, float drop_p) {
-    TTTS_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "%s: bad dims", name);
-    TTTS_REQUIRE((long)B * H < (1L << 31) && cdiv(Tq, QB) <= 65535 && cdiv(Tk, QB) <= 65535, "%s: grid too large", name);
-    TTTS_REQUIRE(ldq >= H * HD && ldk >= H * HD && ldv >= H * HD && ldo >= H * HD, "%s: row strides must be >= H*64", name);
-    TTTS_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0, "%s: row strides must be multiples of 4", name);
+// on top of attn_check: the tile requests address an utterance's operand through a 32-bit buffer descriptor
+static int check_img_spans(const char* name, int Tq, int Tk, int ldq, int ldk, int ldv) {
     TTTS_REQUIRE((uint64_t)Tq * ldq * 4 < (1ull << 32) && (uint64_t)Tk * ldk * 4 < (1ull << 32) && (uint64_t)Tk * ldv * 4 < (1ull << 32),
                  "%s: one utterance's operand exceeds 4 GiB", name);
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: bad dropout p", name);
+    return TTTS_OK;
+}
+// the plane strides of the inverse scales and row statistics (0 = as dense as the batch)
+static int fill_img_planes(const char* name, AttnImgArgs& a, int B, int H, int Tq, int Tk, int64_t q_inv_rows, int64_t k_inv_rows,
+                           int64_t stat_plane) {
+    TTTS_REQUIRE((q_inv_rows == 0 || q_inv_rows >= (int64_t)B * Tq) && (k_inv_rows == 0 || k_inv_rows >= (int64_t)B * Tk) &&
+                 (stat_plane == 0 || stat_plane >= (int64_t)B * H * Tq), "%s: plane strides smaller than the batch", name);
+    a.q_rows = q_inv_rows ? q_inv_rows : (long)B * Tq; a.k_rows = k_inv_rows ? k_inv_rows : (long)B * Tk;
+    a.stat_plane = stat_plane ? stat_plane : (long)B * H * Tq;
     return TTTS_OK;
 }
 
@@ -1312,26 +1292,21 @@ extern "C" int ttts_attention_fwd_img(const void* q, const void* k, const void* 
                                       uint64_t seed, const uint64_t* step_seed, const float* v_amax, float* o_amax_out,
                                       float* rowstat_out, int64_t q_inv_rows, int64_t k_inv_rows, int64_t stat_plane, void* stream) {
     TTTS_REQUIRE(q && k && v && q_inv && k_inv && v_inv && o && key_lens && v_amax, "attention_fwd_img: null pointer");
-    int rc = check_img("attention_fwd_img", B, H, Tq, Tk, ldq, ldk, ldv, ldo, drop_p);
+    int rc = attn_check("attention_fwd_img", HD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = check_img_spans("attention_fwd_img", Tq, Tk, ldq, ldk, ldv);
     if (rc) return rc;
     TTTS_REQUIRE(!(causal && attn), "attention_fwd_img: weights output is only for non-causal (cross) attention");
-    TTTS_REQUIRE(!causal || Tq == Tk, "attention_fwd_img: causal form needs Tq == Tk");
     TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)v_amax) & 15) == 0,
                  "attention_fwd_img: q/k/v/o/v_amax must be 16-byte aligned");
     AttnImgArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    rc = fill_img_planes("attention_fwd_img", a, B, H, Tq, Tk, q_inv_rows, k_inv_rows, stat_plane);
+    if (rc) return rc;
     a.q = q; a.k = k; a.v = v; a.q_inv = q_inv; a.k_inv = k_inv; a.v_inv = v_inv;
-    TTTS_REQUIRE((q_inv_rows == 0 || q_inv_rows >= (int64_t)B * Tq) && (k_inv_rows == 0 || k_inv_rows >= (int64_t)B * Tk) &&
-                 (stat_plane == 0 || stat_plane >= (int64_t)B * H * Tq), "attention_fwd_img: plane strides smaller than the batch");
-    a.q_rows = q_inv_rows ? q_inv_rows : (long)B * Tq; a.k_rows = k_inv_rows ? k_inv_rows : (long)B * Tk;
-    a.stat_plane = stat_plane ? stat_plane : (long)B * H * Tq;
-    a.o = o; a.lse = lse; a.attn = attn; a.key_lens = key_lens;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.thr = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
-    a.drop_scale = 1.f / (1.f - drop_p);
-    a.qscale = q_scale;
-    a.seed = seed; a.step_seed = step_seed;
+    a.o = o; a.lse = lse; a.attn = attn;
     a.v_amax = v_amax; a.o_amax = o_amax_out; a.rowstat = rowstat_out;
     dim3 grid(B * H, cdiv(Tq, QB), 1);
+    // (four cases, not the shared ladder: keys that fit LDS at once have a weights kernel of their own)
     if (causal)
         hipLaunchKernelGGL((attn_fwd_img_kernel<true, false, TTTS_AIMG_KT>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else if (!attn)
@@ -1365,26 +1340,20 @@ extern "C" int ttts_attention_bwd_img(const void* q, const void* k, const void* 
     hipStream_t stream = (hipStream_t)stream_;
     TTTS_REQUIRE(q && k && v && q_inv && k_inv && v_inv && o && d_o && rowstat && delta && dq && dk && dv && key_lens && do_amax,
                  "attention_bwd_img: null pointer");
-    int rc = check_img("attention_bwd_img", B, H, Tq, Tk, ldq, ldk, ldv, ldo, drop_p);
+    int rc = attn_check("attention_bwd_img", HD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = check_img_spans("attention_bwd_img", Tq, Tk, ldq, ldk, ldv);
+    if (!rc) rc = attn_check_grad_strides("attention_bwd_img", HD, H, lddq, lddk, lddv);
     if (rc) return rc;
-    TTTS_REQUIRE(lddq >= H * HD && lddk >= H * HD && lddv >= H * HD, "attention_bwd_img: gradient strides must be >= H*64");
-    TTTS_REQUIRE(!causal || Tq == Tk, "attention_bwd_img: causal form needs Tq == Tk");
     TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o | (uintptr_t)do_amax) & 15) == 0,
                  "attention_bwd_img: q/k/v/o/d_o/do_amax must be 16-byte aligned");
     TTTS_REQUIRE((uint64_t)Tq * ldo * 4 < (1ull << 32), "attention_bwd_img: one utterance's d_o exceeds 4 GiB");
     AttnImgArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    rc = fill_img_planes("attention_bwd_img", a, B, H, Tq, Tk, q_inv_rows, k_inv_rows, stat_plane);
+    if (rc) return rc;
     a.q = q; a.k = k; a.v = v; a.q_inv = q_inv; a.k_inv = k_inv; a.v_inv = v_inv;
-    TTTS_REQUIRE((q_inv_rows == 0 || q_inv_rows >= (int64_t)B * Tq) && (k_inv_rows == 0 || k_inv_rows >= (int64_t)B * Tk) &&
-                 (stat_plane == 0 || stat_plane >= (int64_t)B * H * Tq), "attention_bwd_img: plane strides smaller than the batch");
-    a.q_rows = q_inv_rows ? q_inv_rows : (long)B * Tq; a.k_rows = k_inv_rows ? k_inv_rows : (long)B * Tk;
-    a.stat_plane = stat_plane ? stat_plane : (long)B * H * Tq;
-    a.o = const_cast<float*>(o); a.dout = d_o; a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv; a.key_lens = key_lens;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.o = const_cast<float*>(o); a.dout = d_o; a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
     a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.thr = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
-    a.drop_scale = 1.f / (1.f - drop_p);
-    a.qscale = q_scale;
-    a.seed = seed; a.step_seed = step_seed;
     a.do_amax = do_amax; a.amax_dq = dq_amax_out; a.amax_dkv = dkv_amax_out;
     a.rowstat = const_cast<float*>(rowstat);
     // q_splits > 1: dk / dv as partial sums over q_splits query ranges in dkv_partials (q_splits x B x Tk x 2 H 64 floats), then
@@ -1396,17 +1365,9 @@ extern "C" int ttts_attention_bwd_img(const void* q, const void* k, const void* 
         a.ldp = 2 * H * HD;
         a.dkv_part = dkv_partials; a.part_stride = (long)B * Tk * a.ldp;
     }
-    dim3 gq(B * H, cdiv(Tq, QB), 1), gk(B * H, cdiv(Tk, QB), q_splits);
-    if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dq_img_kernel<true>), gq, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_bwd_dq_img_kernel");
-        hipLaunchKernelGGL((attn_bwd_dkv_img_kernel<true>), gk, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_img_kernel<false>), gq, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_bwd_dq_img_kernel");
-        hipLaunchKernelGGL((attn_bwd_dkv_img_kernel<false>), gk, dim3(256), 0, stream, a);
-    }
-    TTTS_LAUNCH_CHECK("attn_bwd_dkv_img_kernel");
+    rc = ATTN_LAUNCH_BWD(attn_bwd_dq_img_kernel, 0, attn_bwd_dkv_img_kernel, 0, causal, "attention_bwd_img", "attn_bwd_dq_img_kernel",
+                         "attn_bwd_dkv_img_kernel", a, q_splits, stream);
+    if (rc) return rc;
     if (q_splits > 1) {
         const long n4 = a.part_stride / 4;
         const long blocks = (n4 + 255) / 256;

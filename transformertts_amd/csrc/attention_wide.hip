@@ -24,32 +24,6 @@
 
 namespace ttts {
 
-constexpr int WHD = 128;          // columns per (padded) head
-constexpr int WLD = WHD + 1;      // LDS row stride (odd: conflict-free "row per lane" reads)
-constexpr int WKB = 32;           // rows staged per barrier pair (one 32-row MFMA sub-tile)
-// two staged 32-row tiles, re-used as per-wave 32x65 scratch in the epilogue (4 waves x 8320 B = 33280 B)
-constexpr int WSMEM_FLOATS = 4 * 32 * KT_LD;
-static_assert(2 * WKB * WLD <= WSMEM_FLOATS, "staging buffers must fit the shared scratch");
-
-// cooperative staging (256 threads): WKB rows x 128 floats from global into LDS; rows beyond `nrows_total` are zero
-template <bool PADDED>
-__device__ __forceinline__ void wide_stage_rows(const float* base, long row0, long nrows_total, int ld, int tid, float* dst,
-                                                float scale) {
-    constexpr int LDD = PADDED ? WLD : WHD;
-    const RowSrc src = row_src(base, nrows_total, ld);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = row_load4(src, row0 + (tid >> 5) + 8 * i, tid & 31);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float* d = dst + ((tid >> 5) + 8 * i) * LDD + (tid & 31) * 4;
-        if (PADDED) {
-            d[0] = v[i].x * scale; d[1] = v[i].y * scale; d[2] = v[i].z * scale; d[3] = v[i].w * scale;
-        } else {
-            *reinterpret_cast<float4*>(d) = make_float4(v[i].x * scale, v[i].y * scale, v[i].z * scale, v[i].w * scale);
-        }
-    }
-}
 // lane-resident B operand: reg[j] = X[row][64 * half + j] * scale (zeros for a row past the end)
 __device__ __forceinline__ void wide_load_lane_row(const RowSrc& src, long row, int half, float scale, float (&reg)[64]) {
 #pragma unroll
@@ -66,32 +40,6 @@ __device__ __forceinline__ void wide_dot(const float* tile, int l31, int half, c
     for (int j = 0; j < 64; ++j)
         s = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[l31 * WLD + 64 * half + j], reg[j], s, 0, 0, 0);
 }
-// write four 32x32 accumulators holding X^T[d][row] (row on the lane) as rows of 128 floats, one 64-column half at a time
-__device__ __forceinline__ void wide_store_rows(const f32x16 (&acc)[4], float* scratch, float* gbase, long row0,
-                                                long nrows_total, int ld, int lane, float scale) {
-    const int l31 = lane & 31, half = lane >> 5;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) scratch[l31 * KT_LD + blk * 32 + acc_row(r, half)] = acc[2 * hb + blk][r] * scale;
-        wave_lds_sync();
-#pragma unroll 4
-        for (int i = 0; i < 32; ++i) {
-            float v = scratch[i * KT_LD + lane];
-            if (row0 + i < nrows_total) gbase[(row0 + i) * ld + hb * 64 + lane] = v;
-        }
-        wave_lds_sync();
-    }
-}
-__device__ __forceinline__ int wide_klen(const AttnArgs& a, int b) {
-    int klen = (int)a.key_lens[b];
-    if (klen > a.Tk) klen = a.Tk;
-    if (klen < 0) klen = 0;
-    return klen;
-}
-
 // =====================================================================================  forward
 template <bool CAUSAL, bool WRITE_A>
 __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
@@ -112,13 +60,8 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
     const int qg = qw0 + l31;
     float* scratch = smem + wave * 32 * KT_LD;
 
-    const int klen = wide_klen(a, b);
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst_live = (kend + WKB - 1) / WKB;
-    const int nst = WRITE_A ? (a.Tk + WKB - 1) / WKB : nst_live;
-    int wave_kend = WRITE_A ? a.Tk : kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, WRITE_A, WKB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * WHD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * WHD;
@@ -137,22 +80,13 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
     const long arow = ((long)(b * a.H + h) * a.Tq);   // row base of the (B,H,Tq,*) outputs
     const uint32_t rowid = (uint32_t)(arow + qg);
 
-    auto alive = [&](int key_g) -> bool { return key_g < klen && (!CAUSAL || key_g <= qg); };
-    // registers r .. r+3 of a lane are four neighbouring keys: one hash
-    auto drop16 = [&](float (&p)[16], int key0) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {
-            const uint32_t qh = attn_quad_hash(seed_eff, rowid, (uint32_t)(key0 + acc_row(r, half)) >> 2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) p[r + e] = attn_keep_word(qh, attn_drop_mult(e), thr16) ? p[r + e] * a.drop_scale : 0.f;
-        }
-    };
+    auto drop16 = [&](float (&p)[16], int key0) { attn_drop16<true>(p, seed_eff, rowid, key0, half, thr16, a.drop_scale); };
     // online row max / row sum over one masked score tile; -> the factor the running sums shrink by
     auto online = [&](f32x16& s, int key0, float (&p)[16]) -> float {
         float mx = NEG_INF;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            s[r] = alive(key0 + acc_row(r, half)) ? s[r] : NEG_INF;
+            s[r] = attn_alive<CAUSAL>(key0 + acc_row(r, half), klen, qg) ? s[r] : NEG_INF;
             mx = fmaxf(mx, s[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -169,9 +103,9 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
 
     if (WRITE_A) {
         // ---------------- pass 1: row max / row sum only
-        for (int t = 0; t < nst_live; ++t) {
+        for (int t = 0; t < kr.nst_live; ++t) {
             __syncthreads();
-            wide_stage_rows<true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
+            stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
             __syncthreads();
             f32x16 s;
             float p[16];
@@ -185,19 +119,19 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
     const float inv_l = (l > 0.f) ? 1.f / l : 0.f;
 
     // ---------------- main pass
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
-        wide_stage_rows<true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
-        wide_stage_rows<false>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
+        stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
+        stage_rows<WHD, false>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
         const int key0 = t * WKB;
-        if (key0 < wave_kend) {      // else: tile entirely above this wave's causal frontier / past the keys
+        if (key0 < kr.wave_kend) {      // else: tile entirely above this wave's causal frontier / past the keys
             f32x16 s;
             wide_dot(Ks, l31, half, qreg, s);
             float p[16];
             if (WRITE_A) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) p[r] = alive(key0 + acc_row(r, half)) ? __expf(s[r] - m_fin) * inv_l : 0.f;
+                for (int r = 0; r < 16; ++r) p[r] = attn_alive<CAUSAL>(key0 + acc_row(r, half), klen, qg) ? __expf(s[r] - m_fin) * inv_l : 0.f;
             } else {
                 const float alpha = online(s, key0, p);
 #pragma unroll
@@ -245,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[blk][r] *= out_scale;
     __syncthreads();
-    wide_store_rows(o, scratch, a.o + (long)b * a.Tq * a.ldo + h * WHD, qw0, a.Tq, a.ldo, lane, 1.f);
+    wave_store_rows(o, scratch, a.o + (long)b * a.Tq * a.ldo + h * WHD, qw0, a.Tq, a.ldo, lane, 1.f);
 }
 
 // =====================================================================================  backward: dQ (+ delta)
@@ -265,12 +199,8 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
     const int qg = qw0 + l31;
     float* scratch = smem + wave * 32 * KT_LD;
 
-    const int klen = wide_klen(a, b);
-    int kend = klen;
-    if (CAUSAL && kend > q0 + QB) kend = q0 + QB;
-    const int nst = (kend + WKB - 1) / WKB;
-    int wave_kend = kend;
-    if (CAUSAL && wave_kend > qw0 + 32) wave_kend = qw0 + 32;
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
+    const KeyRange kr = key_range<CAUSAL, false, WKB>(klen, a.Tk, q0, qw0);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * WHD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * WHD;
@@ -305,13 +235,13 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[blk][r] = 0.f;
 
-    for (int t = 0; t < nst; ++t) {
+    for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
-        wide_stage_rows<true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
-        wide_stage_rows<true>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
+        stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
+        stage_rows<WHD, true>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
         const int key0 = t * WKB;
-        if (key0 < wave_kend) {
+        if (key0 < kr.wave_kend) {
             f32x16 s, dp;
             wide_dot(Ks, l31, half, qreg, s);
             wide_dot(Vs, l31, half, greg, dp);
@@ -324,10 +254,9 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int kg = key_g + e;
-                    const bool live = kg < klen && (!CAUSAL || kg <= qg);
-                    const float p = live ? __expf(s[r + e] - m_q) * inv_l : 0.f;
+                    const float p = attn_alive<CAUSAL>(kg, klen, qg) ? __expf(s[r + e] - m_q) * inv_l : 0.f;
                     float g = dp[r + e];
-                    if (a.thr != 0u) g = attn_keep_word(qh, attn_drop_mult(e), thr16) ? g * a.drop_scale : 0.f;
+                    if (a.thr != 0u) g = attn_drop1<true>(g, qh, e, thr16, a.drop_scale);
                     ds[r + e] = one_hot ? 0.f : p * (g - delta);
                 }
             }
@@ -341,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
         }
     }
     __syncthreads();
-    wide_store_rows(dq, scratch, a.dq + (long)b * a.Tq * a.lddq + h * WHD, qw0, a.Tq, a.lddq, lane, a.qscale);
+    wave_store_rows(dq, scratch, a.dq + (long)b * a.Tq * a.lddq + h * WHD, qw0, a.Tq, a.lddq, lane, a.qscale);
 }
 
 // =====================================================================================  backward: dK, dV
@@ -362,7 +291,7 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
     const int kg = kw0 + l31;
     float* scratch = smem + wave * 32 * KT_LD;
 
-    const int klen = wide_klen(a, b);
+    const int klen = attn_klen(a.key_lens, b, a.Tk);
 
     const float* qb_ = a.q + (long)b * a.Tq * a.ldq + h * WHD;
     const float* kb_ = a.k + (long)b * a.Tk * a.ldk + h * WHD;
@@ -382,13 +311,12 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
         for (int r = 0; r < 16; ++r) { dk[blk][r] = 0.f; dv[blk][r] = 0.f; }
 
     const int nqs = (a.Tq + WKB - 1) / WKB;
-    int qs_begin = CAUSAL ? (k0 / WKB) : 0;       // queries below the block's first key never see it
-    if (k0 >= klen) qs_begin = nqs;               // whole key block is padding: gradients are zero
+    const int qs_begin = attn_qs_begin<CAUSAL, WKB>(k0, klen, nqs);
 
     for (int qs = qs_begin; qs < nqs; ++qs) {
         __syncthreads();
-        wide_stage_rows<true>(qb_, (long)qs * WKB, a.Tq, a.ldq, tid, Qs, a.qscale);
-        wide_stage_rows<true>(gb_, (long)qs * WKB, a.Tq, a.ldo, tid, Gs, 1.f);
+        stage_rows<WHD, true>(qb_, (long)qs * WKB, a.Tq, a.ldq, tid, Qs, a.qscale);
+        stage_rows<WHD, true>(gb_, (long)qs * WKB, a.Tq, a.ldo, tid, Gs, 1.f);
         if (tid < WKB) {
             const int q = qs * WKB + tid;
             const float lq = (q < a.Tq) ? a.rowstat[plane + arow + q] : 0.f;
@@ -408,7 +336,7 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int qrow = acc_row(r, half);
                 const int q_g = qt0 + qrow;
-                const bool live = kg < klen && (!CAUSAL || kg <= q_g) && q_g < a.Tq;
+                const bool live = attn_alive<CAUSAL>(kg, klen, q_g) && q_g < a.Tq;
                 const float p = live ? __expf(s[r] - m_s[qrow]) * il_s[qrow] : 0.f;
                 float g = dp[r];
                 float pk = p;
@@ -432,23 +360,8 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
         }
     }
     __syncthreads();
-    wide_store_rows(dk, scratch, a.dk + (long)b * a.Tk * a.lddk + h * WHD, kw0, a.Tk, a.lddk, lane, 1.f);
-    wide_store_rows(dv, scratch, a.dv + (long)b * a.Tk * a.lddv + h * WHD, kw0, a.Tk, a.lddv, lane, 1.f);
-}
-
-// arguments both entry points share; every refusal names the value it refuses
-static int wide_check(const char* name, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int causal,
-                      float drop_p) {
-    TTTS_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "%s: sizes must be positive (B %d, H %d, Tq %d, Tk %d)", name, B, H, Tq, Tk);
-    TTTS_REQUIRE((long)B * H < (1L << 31) && cdiv(Tq, QB) <= 65535 && cdiv(Tk, QB) <= 65535,
-                 "%s: grid too large (B*H %ld, Tq %d, Tk %d)", name, (long)B * H, Tq, Tk);
-    TTTS_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0,
-                 "%s: row strides must be multiples of 4 floats (ldq %d, ldk %d, ldv %d, ldo %d)", name, ldq, ldk, ldv, ldo);
-    TTTS_REQUIRE(ldq >= H * WHD && ldk >= H * WHD && ldv >= H * WHD && ldo >= H * WHD,
-                 "%s: row strides must be >= H*128 = %d (ldq %d, ldk %d, ldv %d, ldo %d)", name, H * WHD, ldq, ldk, ldv, ldo);
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: dropout p %g is outside [0, 1)", name, (double)drop_p);
-    TTTS_REQUIRE(!causal || Tq == Tk, "%s: the causal form needs Tq == Tk (Tq %d, Tk %d)", name, Tq, Tk);
-    return TTTS_OK;
+    wave_store_rows(dk, scratch, a.dk + (long)b * a.Tk * a.lddk + h * WHD, kw0, a.Tk, a.lddk, lane, 1.f);
+    wave_store_rows(dv, scratch, a.dv + (long)b * a.Tk * a.lddv + h * WHD, kw0, a.Tk, a.lddv, lane, 1.f);
 }
 
 }  // namespace ttts
@@ -459,64 +372,35 @@ extern "C" {
 
 int ttts_attention_fwd_wide(const float* q, const float* k, const float* v, float* o, float* rowstat, float* attn,
                             const int64_t* key_lens, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo,
-                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream) {
     TTTS_REQUIRE(q && k && v && o && rowstat && key_lens, "attention_fwd_wide: null pointer");
-    int rc = wide_check("attention_fwd_wide", B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    int rc = attn_check("attention_fwd_wide", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
     if (rc) return rc;
     TTTS_REQUIRE(!(causal && attn), "attention_fwd_wide: the weights are only written by the non-causal (cross) form");
     TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "attention_fwd_wide: q/k/v must be 16-byte aligned");
     AttnArgs a = {};
-    a.q = q; a.k = k; a.v = v; a.o = o; a.rowstat = rowstat; a.attn = attn; a.key_lens = key_lens;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.thr = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
-    a.drop_scale = 1.f / (1.f - drop_p);
-    a.qscale = q_scale;
-    a.seed = seed; a.step_seed = step_seed;
-    dim3 grid(B * H, cdiv(Tq, QB), 1);
-    if (causal)
-        hipLaunchKernelGGL((attn_wide_fwd_kernel<true, false>), grid, dim3(256), 0, stream, a);
-    else if (attn)
-        hipLaunchKernelGGL((attn_wide_fwd_kernel<false, true>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((attn_wide_fwd_kernel<false, false>), grid, dim3(256), 0, stream, a);
-    TTTS_LAUNCH_CHECK("attn_wide_fwd_kernel");
-    return TTTS_OK;
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.rowstat = rowstat; a.attn = attn;
+    return attn_launch_fwd("attn_wide_fwd_kernel", ATTN_FWD_FORMS(attn_wide_fwd_kernel), causal, attn != nullptr, a, (hipStream_t)stream);
 }
 
 int ttts_attention_bwd_wide(const float* q, const float* k, const float* v, const float* o, const float* d_o,
                             const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
                             int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
-                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream) {
     TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "attention_bwd_wide: null pointer");
-    int rc = wide_check("attention_bwd_wide", B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    int rc = attn_check("attention_bwd_wide", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = attn_check_grad_strides("attention_bwd_wide", WHD, H, lddq, lddk, lddv);
     if (rc) return rc;
-    TTTS_REQUIRE(lddq >= H * WHD && lddk >= H * WHD && lddv >= H * WHD,
-                 "attention_bwd_wide: gradient strides must be >= H*128 = %d (lddq %d, lddk %d, lddv %d)", H * WHD, lddq, lddk, lddv);
     TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
                  "attention_bwd_wide: q/k/v/o/d_o must be 16-byte aligned");
     AttnArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
     a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
-    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv; a.key_lens = key_lens;
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
     a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.thr = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
-    a.drop_scale = 1.f / (1.f - drop_p);
-    a.qscale = q_scale;
-    a.seed = seed; a.step_seed = step_seed;
-    dim3 gq(B * H, cdiv(Tq, QB), 1), gk(B * H, cdiv(Tk, QB), 1);
-    if (causal) {
-        hipLaunchKernelGGL((attn_wide_bwd_dq_kernel<true>), gq, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_wide_bwd_dq_kernel");
-        hipLaunchKernelGGL((attn_wide_bwd_dkv_kernel<true>), gk, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((attn_wide_bwd_dq_kernel<false>), gq, dim3(256), 0, stream, a);
-        TTTS_LAUNCH_CHECK("attn_wide_bwd_dq_kernel");
-        hipLaunchKernelGGL((attn_wide_bwd_dkv_kernel<false>), gk, dim3(256), 0, stream, a);
-    }
-    TTTS_LAUNCH_CHECK("attn_wide_bwd_dkv_kernel");
-    return TTTS_OK;
+    return ATTN_LAUNCH_BWD(attn_wide_bwd_dq_kernel, 0, attn_wide_bwd_dkv_kernel, 0, causal, "attention_bwd_wide", "attn_wide_bwd_dq_kernel",
+                           "attn_wide_bwd_dkv_kernel", a, 1, (hipStream_t)stream);
 }
 
 }  // extern "C"
