@@ -433,6 +433,33 @@ int ttts_attention_bwd_wide(const float* q, const float* k, const float* v, cons
                             const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
                             int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
                             int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream);
+/* ---- the 128-column attention under masks that are tensors (ABI v18; attention_wide.hip): the call sites above when the layer
+ * is given a `src_key_padding_mask` / `tgt_key_padding_mask` / `memory_key_padding_mask` with holes, a `memory_mask`, or a
+ * `mask` / `tgt_mask` that is not the causal one (arguments of model/layers.py:29-74 -> `_sa_block` / `_mha_block` ->
+ * F.multi_head_attention_forward, which merges them into one float attn_mask, torch/nn/functional.py:6404-6436, and adds it to
+ * the scaled scores, torch/nn/functional.py:6578-6586 resp. scaled_dot_product_attention's attn_mask, :6629).  Arguments of the
+ * _wide entry points plus:
+ *   add_mask   NULL, or fp32: element (b, h, q, key) at add_mask[b*mask_stride_b + h*mask_stride_h + q*ldm + key] (strides in
+ *              elements, 0 = broadcast: torch's (Tq, Tk) form is 0 / 0, its (B*H, Tq, Tk) form H*Tq*ldm / Tq*ldm).  A value at
+ *              or below half the lowest finite float (-inf, finfo.min) forbids the key; any other value is added to the scaled
+ *              score q_scale * q.k.  ldm is a multiple of 4 floats and >= Tk, every slice 16-byte aligned and below 4 GiB.
+ *   key_dead   NULL, or (B, ldd) bytes, ldd >= Tk: non-zero = the key is not attended to.
+ * A key is alive iff key < key_lens[b] && !dead && !forbidden && (!causal || key <= q); with key_dead the caller may pass
+ * key_lens = one past the last live key.  A query row without an alive key gives zeros in o and attn, m = l = 0 in rowstat, a
+ * zero dq row and no contribution to dk / dv.  Dropout, the post-dropout weights, rowstat and the one-hot rule are those of
+ * the _wide entry points (same hash, same row ids).  Refused before any launch, naming the value: both masks NULL, ldm < Tk or
+ * no multiple of 4, a misaligned mask, negative strides, ldd < Tk, weights together with causal. */
+int ttts_attention_fwd_wide_masked(const float* q, const float* k, const float* v, float* o, float* rowstat, float* attn,
+                                   const int64_t* key_lens, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo,
+                                   int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                                   const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
+                                   const uint8_t* key_dead, int64_t ldd, void* stream);
+int ttts_attention_bwd_wide_masked(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                                   const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
+                                   int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
+                                   int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                                   const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
+                                   const uint8_t* key_dead, int64_t ldd, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

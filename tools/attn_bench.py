@@ -6,7 +6,11 @@ A/B two builds with TTTS_LIB=<lib>.
     --head-dim N (default 64): N > 64 runs the `wide` configuration's shapes (B=8, H=8; causal self T=870, self T=100, cross
     870 x 100 WITH weights) on the 128-column fp32-MFMA kernels and, interleaved with them round by round in the same process,
     on ops.masked_attention -- stock torch differentiated by autograd, the route these head widths took before the kernels
-    existed -- and prints forward + backward time and peak memory of both."""
+    existed -- and prints forward + backward time and peak memory of both.
+
+    --masked: the same three shapes at head_dim 128 and the base model's (B=64, H=4, head_dim 64, padded to 128 columns) under a
+    2-D band mask plus a key-padding mask with holes: the masked 128-column kernels (ops.self_attention / ops.cross_attention
+    with `dead` / `add_mask`) against ops.masked_attention on the same masks, interleaved the same way."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,25 +22,32 @@ def ev():
     return torch.cuda.Event(enable_timing=True)
 
 
-def run_wide(name, B, H, hd, Tq, Tk, causal, need_w, p=0.1, rounds=5, reps=4):
+def run_wide(name, B, H, hd, Tq, Tk, causal, need_w, p=0.1, rounds=5, reps=4, masked=False):
     """kernels against the torch route, alternating (A B A B ...): min and median of forward + backward, peak bytes above what
-    was live before the call"""
+    was live before the call.  `masked`: a band of half-width Tk / 8 along the diagonal as a shared (Tq, Tk) float mask (the
+    band's scores get a random bias) and 10 % dead keys"""
     d = H * hd
     torch.manual_seed(0)
     lens = torch.full((B,), Tk, dtype=torch.int64, device=dev)
+    dead = add = add_finite = None
+    if masked:
+        dead = torch.rand(B, Tk, device=dev) < 0.1
+        off = (torch.arange(Tq, device=dev)[:, None] * Tk // Tq - torch.arange(Tk, device=dev)[None, :]).abs()
+        add = ops.pad_mask_rows(torch.randn(Tq, Tk, device=dev).masked_fill(off > max(Tk // 8, 1), float("-inf")))
+        add_finite = add.clamp_min(torch.finfo(torch.float32).min)[None, None]
     q = torch.randn(B, Tq, 3 * d if Tq == Tk else d, device=dev, requires_grad=True)
     kv = None if Tq == Tk else torch.randn(B, Tk, 2 * d, device=dev, requires_grad=True)
     do = torch.randn(B, Tq, d, device=dev)
 
     def kernels():
         if kv is None:
-            return ops.self_attention(q, lens, H, bool(causal), p, 7)
-        return ops.cross_attention(q, kv, lens, H, p, 7, need_w)[0]
+            return ops.self_attention(q, lens, H, bool(causal), p, 7, dead=dead, add_mask=add)
+        return ops.cross_attention(q, kv, lens, H, p, 7, need_w, dead=dead, add_mask=add)[0]
 
     def torch_route():
         if kv is None:
-            return ops.masked_attention(q[..., :d], q[..., d:2 * d], q[..., 2 * d:], lens, H, bool(causal), p)[0]
-        return ops.masked_attention(q, kv[..., :d], kv[..., d:], lens, H, False, p)[0]
+            return ops.masked_attention(q[..., :d], q[..., d:2 * d], q[..., 2 * d:], lens, H, bool(causal), p, dead, add_finite)[0]
+        return ops.masked_attention(q, kv[..., :d], kv[..., d:], lens, H, False, p, dead, add_finite)[0]
 
     times, peak = {"kernels": [], "torch": []}, {}
     for rnd in range(rounds + 1):                 # round 0 warms both up
@@ -104,8 +115,14 @@ def run(name, B, H, Tq, Tk, causal, p=0.1, reps=8):
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--head-dim", type=int, default=64)
+ap.add_argument("--masked", action="store_true")
 args = ap.parse_args()
-if args.head_dim > 64:
+if args.masked:
+    for B, H, hd in ((8, 8, 128), (64, 4, 64)):
+        run_wide("causal self", B, H, hd, 870, 870, 1, False, masked=True)
+        run_wide("self", B, H, hd, 100, 100, 0, False, masked=True)
+        run_wide("cross+weights", B, H, hd, 870, 100, 0, True, masked=True)
+elif args.head_dim > 64:
     run_wide("causal self", 8, 8, args.head_dim, 870, 870, 1, False)
     run_wide("self", 8, 8, args.head_dim, 100, 100, 0, False)
     run_wide("cross+weights", 8, 8, args.head_dim, 870, 100, 0, True)

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Compare two `hipcc -S` outputs (files, or directories of *.s matched by name) kernel by kernel.
 
-    python tools/isa_diff.py OLD NEW
+    python tools/isa_diff.py OLD NEW [--rename REGEX=REPLACEMENT ...]
+
+--rename rewrites the names of NEW's kernels (re.sub, in the order given) before they are matched with OLD's: for a kernel whose
+code is meant to be the same but whose mangled name moved, e.g. a template that gained a defaulted argument.
 
 Per kernel: VGPR / AGPR / SGPR counts, scratch and LDS bytes, and every opcode whose count differs.  Exit status 1 when a
 resource differs, a kernel is missing, or an opcode outside the scalar ALU differs in count; scalar-ALU differences (s_*
@@ -45,8 +48,13 @@ def kernels(path):
     return {k: (res[k], ops[k]) for k in res}, no_register
 
 
-def main(old, new):
+def main(old, new, renames=()):
     (a, na), (b, nb) = kernels(old), kernels(new)
+    for pattern, repl in renames:
+        renamed = {re.sub(pattern, repl, name): v for name, v in b.items()}
+        if len(renamed) != len(b):
+            sys.exit(f"--rename {pattern}={repl}: two kernels of NEW get the same name")
+        b = renamed
     no_register = na | nb
     bad = 0
     for name in sorted(set(a) | set(b)):
@@ -68,6 +76,13 @@ def main(old, new):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        if i + 1 >= len(args) or "=" not in args[i + 1]:
+            sys.exit(__doc__)
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1], renames))

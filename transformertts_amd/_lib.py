@@ -85,6 +85,9 @@ SIGNATURES = {
                                    P, I, L, L, L, P]),
     "ttts_attention_fwd_wide": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U, P, P]),
     "ttts_attention_bwd_wide": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, P]),
+    "ttts_attention_fwd_wide_masked": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U, P, P, L, L, L, P, L, P]),
+    "ttts_attention_bwd_wide_masked": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, P, L, L, L,
+                                           P, L, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

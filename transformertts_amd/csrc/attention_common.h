@@ -179,6 +179,57 @@ __device__ __forceinline__ int attn_qs_begin(int k0, int klen, int nqs) {
 template <bool CAUSAL>
 __device__ __forceinline__ bool attn_alive(int key, int klen, int q) { return key < klen && (!CAUSAL || key <= q); }
 
+// ---- masks that arrive as tensors (the MASKED forms of the 128-column kernels): an additive fp32 mask per (batch, head) slice
+// (row stride ldm floats, a multiple of 4; batch / head strides in elements, 0 = broadcast) and a (B, ldd) byte mask of dead keys;
+// either may be NULL.  A mask element at or below MASK_FORBID (half the lowest finite float: what -inf and torch's
+// finfo.min fill both satisfy; a NaN fails the comparison and forbids too) forbids the key, any other value is added to the
+// scaled score.
+struct AttnMaskArgs : AttnArgs {
+    const float* add_mask; const uint8_t* key_dead;
+    long mask_stride_b, mask_stride_h;
+    int ldm, ldd;
+};
+constexpr float MASK_FORBID = -1.7014117e38f;      // 0.5 * -FLT_MAX
+template <bool CAUSAL>
+__device__ __forceinline__ bool attn_alive_masked(int key, int klen, int q, bool dead, float add) {
+    return attn_alive<CAUSAL>(key, klen, q) && !dead && add > MASK_FORBID;
+}
+// the (Tq, ldm) mask slice of (b, h) behind a buffer descriptor: rows past Tq and a NULL mask (an empty descriptor) read as
+// zeros -- "add nothing, forbid nothing" --, so no mask load sits behind a branch
+__device__ __forceinline__ RowSrc mask_src(const AttnMaskArgs& a, int b, int h) {
+    const float* base = a.add_mask ? a.add_mask + b * a.mask_stride_b + h * a.mask_stride_h : nullptr;
+    return row_src(base, a.add_mask ? a.Tq : 0, a.ldm);
+}
+// query on the lane (forward, dQ): the lane's four aligned key quads of the 32-key tile at key0 -- registers 4 i .. 4 i + 3 --
+// as four 16-byte loads of its mask row
+__device__ __forceinline__ void mask_load_row16(const RowSrc& src, long q, int key0, int half, float (&mk)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 v = row_load4(src, q, (key0 >> 2) + 2 * i + half);
+        mk[4 * i] = v.x; mk[4 * i + 1] = v.y; mk[4 * i + 2] = v.z; mk[4 * i + 3] = v.w;
+    }
+}
+// key on the lane (dK / dV): the 16 queries of the lane's accumulator rows, one dword each, coalesced across the 32 key lanes
+__device__ __forceinline__ void mask_load_col16(const RowSrc& src, int q0, int key, int half, float (&mk)[16]) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        mk[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+            src.rsrc, (int)(uint32_t)(((long)(q0 + acc_row(r, half)) * src.ld + key) * 4), 0, 0));
+}
+// the dead-key bytes of utterance b behind a descriptor of Tk bytes (NULL: empty, nothing dead); one byte per lane
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dead_src(const AttnMaskArgs& a, int b) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.key_dead ? a.key_dead + (long)b * a.ldd : nullptr), 0,
+                                             a.key_dead ? (uint32_t)a.Tk : 0u, 0x00020000);
+}
+__device__ __forceinline__ bool dead_load(__amdgpu_buffer_rsrc_t rsrc, int key) {
+    return __builtin_amdgcn_raw_buffer_load_b8(rsrc, key, 0, 0) != 0;
+}
+// ... and of a 32-key tile as one wave-uniform word (bit j = key0 + j is dead), shifted so that bit acc_row(r, 0) is the
+// lane's register r
+__device__ __forceinline__ uint32_t dead_tile_bits(__amdgpu_buffer_rsrc_t rsrc, int key0, int l31, int half) {
+    return (uint32_t)__ballot(dead_load(rsrc, key0 + l31)) >> (4 * half);
+}
+
 // ---- dropout of a lane's weights: registers r .. r+3 of a lane are four neighbouring keys and share one hash word `qh` (of
 // the quad of `key`); SCALE: the kept ones are multiplied by 1/(1-p) here (else that factor rides in a later scale)
 template <bool SCALE>

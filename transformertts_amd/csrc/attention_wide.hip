@@ -20,6 +20,7 @@
 // the forward's own probabilities whatever the scores' magnitude (from lse alone they are only good to ulp(lse)).  A row
 // whose l is exactly 1.0f is one-hot in fp32: torch's softmax backward of such a row is exactly zero, so its score
 // gradient is taken as zero instead of the rounding of delta against dP.
+#include <type_traits>
 #include "attention_common.h"
 
 namespace ttts {
@@ -41,8 +42,13 @@ __device__ __forceinline__ void wide_dot(const float* tile, int l31, int half, c
         s = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[l31 * WLD + 64 * half + j], reg[j], s, 0, 0, 0);
 }
 // =====================================================================================  forward
-template <bool CAUSAL, bool WRITE_A>
-__global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
+// MASKED (every kernel of this file): the masks are tensors (AttnMaskArgs) on top of the ones derived from `key_lens` -- see
+// attn_alive_masked.  The mask loads are issued with the stage's operand loads; a row that no key is left for gives zeros like
+// an utterance without keys.
+template <bool MASKED> using WideArgs = std::conditional_t<MASKED, AttnMaskArgs, AttnArgs>;
+
+template <bool CAUSAL, bool WRITE_A, bool MASKED = false>
+__global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(WideArgs<MASKED> a) {
     const uint64_t seed_eff = site_seed(a.seed, a.step_seed);
     const uint32_t thr16 = a.thr << 16;
     __shared__ __attribute__((aligned(16))) float smem[WSMEM_FLOATS];
@@ -80,14 +86,29 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
     const long arow = ((long)(b * a.H + h) * a.Tq);   // row base of the (B,H,Tq,*) outputs
     const uint32_t rowid = (uint32_t)(arow + qg);
 
+    // MASKED: the lane's 16 mask values and the tile's dead-key bits of the stage in flight (unused otherwise)
+    float mk[MASKED ? 16 : 1];
+    uint32_t dbits = 0;
+    RowSrc msrc;
+    __amdgpu_buffer_rsrc_t dsrc;
+    if constexpr (MASKED) { msrc = mask_src(a, b, h); dsrc = dead_src(a, b); }
+
     auto drop16 = [&](float (&p)[16], int key0) { attn_drop16<true>(p, seed_eff, rowid, key0, half, thr16, a.drop_scale); };
     // online row max / row sum over one masked score tile; -> the factor the running sums shrink by
     auto online = [&](f32x16& s, int key0, float (&p)[16]) -> float {
         float mx = NEG_INF;
+        if constexpr (MASKED) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = attn_alive<CAUSAL>(key0 + acc_row(r, half), klen, qg) ? s[r] : NEG_INF;
-            mx = fmaxf(mx, s[r]);
+            for (int r = 0; r < 16; ++r) {
+                s[r] = attn_alive_masked<CAUSAL>(key0 + acc_row(r, half), klen, qg, (dbits >> acc_row(r, 0)) & 1u, mk[r]) ? s[r] + mk[r] : NEG_INF;
+                mx = fmaxf(mx, s[r]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                s[r] = attn_alive<CAUSAL>(key0 + acc_row(r, half), klen, qg) ? s[r] : NEG_INF;
+                mx = fmaxf(mx, s[r]);
+            }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float m_new = fmaxf(m, mx);
@@ -105,6 +126,10 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
         // ---------------- pass 1: row max / row sum only
         for (int t = 0; t < kr.nst_live; ++t) {
             __syncthreads();
+            if constexpr (MASKED) {
+                mask_load_row16(msrc, qg, t * WKB, half, mk);
+                dbits = dead_tile_bits(dsrc, t * WKB, l31, half);
+            }
             stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
             __syncthreads();
             f32x16 s;
@@ -121,6 +146,10 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
     // ---------------- main pass
     for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
+        if constexpr (MASKED) {
+            mask_load_row16(msrc, qg, t * WKB, half, mk);
+            dbits = dead_tile_bits(dsrc, t * WKB, l31, half);
+        }
         stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
         stage_rows<WHD, false>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
@@ -129,7 +158,12 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
             f32x16 s;
             wide_dot(Ks, l31, half, qreg, s);
             float p[16];
-            if (WRITE_A) {
+            if (WRITE_A && MASKED) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    p[r] = attn_alive_masked<CAUSAL>(key0 + acc_row(r, half), klen, qg, (dbits >> acc_row(r, 0)) & 1u, mk[r])
+                               ? __expf((s[r] + mk[r]) - m_fin) * inv_l : 0.f;
+            } else if (WRITE_A) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) p[r] = attn_alive<CAUSAL>(key0 + acc_row(r, half), klen, qg) ? __expf(s[r] - m_fin) * inv_l : 0.f;
             } else {
@@ -183,8 +217,8 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(AttnArgs a) {
 }
 
 // =====================================================================================  backward: dQ (+ delta)
-template <bool CAUSAL>
-__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
+template <bool CAUSAL, bool MASKED = false>
+__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKED> a) {
     const uint64_t seed_eff = site_seed(a.seed, a.step_seed);
     const uint32_t thr16 = a.thr << 16;
     __shared__ __attribute__((aligned(16))) float smem[WSMEM_FLOATS];
@@ -235,8 +269,18 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[blk][r] = 0.f;
 
+    float mk[MASKED ? 16 : 1];
+    uint32_t dbits = 0;
+    RowSrc msrc;
+    __amdgpu_buffer_rsrc_t dsrc;
+    if constexpr (MASKED) { msrc = mask_src(a, b, h); dsrc = dead_src(a, b); }
+
     for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
+        if constexpr (MASKED) {
+            mask_load_row16(msrc, qg, t * WKB, half, mk);
+            dbits = dead_tile_bits(dsrc, t * WKB, l31, half);
+        }
         stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
         stage_rows<WHD, true>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
@@ -249,14 +293,22 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; r += 4) {
                 const int key_g = key0 + acc_row(r, half);
+                // MASKED: the hash is taken and applied whether dropout is on or not (thr16 = 0 keeps everything, at scale 1): a
+                // branch on `a.thr` right behind the dP MFMAs would leave its shorter side too few wait states before the first
+                // read of their accumulator ("A read that came too early")
                 uint32_t qh = 0;
-                if (a.thr != 0u) qh = attn_quad_hash(seed_eff, rowid, (uint32_t)key_g >> 2);
+                if (MASKED || a.thr != 0u) qh = attn_quad_hash(seed_eff, rowid, (uint32_t)key_g >> 2);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int kg = key_g + e;
-                    const float p = attn_alive<CAUSAL>(kg, klen, qg) ? __expf(s[r + e] - m_q) * inv_l : 0.f;
+                    float p;
+                    if constexpr (MASKED)
+                        p = attn_alive_masked<CAUSAL>(kg, klen, qg, (dbits >> acc_row(r + e, 0)) & 1u, mk[r + e])
+                                ? __expf((s[r + e] + mk[r + e]) - m_q) * inv_l : 0.f;
+                    else
+                        p = attn_alive<CAUSAL>(kg, klen, qg) ? __expf(s[r + e] - m_q) * inv_l : 0.f;
                     float g = dp[r + e];
-                    if (a.thr != 0u) g = attn_drop1<true>(g, qh, e, thr16, a.drop_scale);
+                    if (MASKED || a.thr != 0u) g = attn_drop1<true>(g, qh, e, thr16, a.drop_scale);
                     ds[r + e] = one_hot ? 0.f : p * (g - delta);
                 }
             }
@@ -274,8 +326,8 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(AttnArgs a) {
 }
 
 // =====================================================================================  backward: dK, dV
-template <bool CAUSAL>
-__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
+template <bool CAUSAL, bool MASKED = false>
+__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideArgs<MASKED> a) {
     const uint64_t seed_eff = site_seed(a.seed, a.step_seed);
     const uint32_t thr16 = a.thr << 16;
     __shared__ __attribute__((aligned(16))) float smem[WSMEM_FLOATS];
@@ -313,10 +365,24 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
     const int nqs = (a.Tq + WKB - 1) / WKB;
     const int qs_begin = attn_qs_begin<CAUSAL, WKB>(k0, klen, nqs);
 
+    // MASKED: the lane's key is dead or not once and for all; its mask column arrives 16 queries per stage and waits in a
+    // lane-private LDS column like the staged operands (held in registers across the stage it costs the causal form a spill)
+    __shared__ float mask_s[MASKED ? 4 * 16 * 64 : 1];
+    float* mcol = mask_s + (MASKED ? wave * 16 * 64 + lane : 0);
+    bool kdead = false;
+    RowSrc msrc;
+    if constexpr (MASKED) { msrc = mask_src(a, b, h); kdead = dead_load(dead_src(a, b), kg); }
+
     for (int qs = qs_begin; qs < nqs; ++qs) {
         __syncthreads();
         stage_rows<WHD, true>(qb_, (long)qs * WKB, a.Tq, a.ldq, tid, Qs, a.qscale);
         stage_rows<WHD, true>(gb_, (long)qs * WKB, a.Tq, a.ldo, tid, Gs, 1.f);
+        if constexpr (MASKED) {
+            float mk[16];
+            mask_load_col16(msrc, qs * WKB, kg, half, mk);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mcol[r * 64] = mk[r];
+        }
         if (tid < WKB) {
             const int q = qs * WKB + tid;
             const float lq = (q < a.Tq) ? a.rowstat[plane + arow + q] : 0.f;
@@ -330,14 +396,34 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(AttnArgs a) {
         if (!CAUSAL || qt0 + 31 >= kw0) {         // else: every query of the tile precedes this wave's keys
             f32x16 s, dp;
             wide_dot(Qs, l31, half, kreg, s);
+            uint32_t okbits = 0;      // MASKED: bit r = the key is alive for the query of register r, a query there is (the mask values end here)
+            if constexpr (MASKED) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float mk = mcol[r * 64];
+                    const int q_g = qt0 + acc_row(r, half);
+                    okbits |= (uint32_t)(attn_alive_masked<CAUSAL>(kg, klen, q_g, kdead, mk) & (q_g < a.Tq)) << r;
+                    s[r] += mk;
+                }
+            }
             wide_dot(Gs, l31, half, vreg, dp);
             float pd[16], ds[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int qrow = acc_row(r, half);
                 const int q_g = qt0 + qrow;
-                const bool live = attn_alive<CAUSAL>(kg, klen, q_g) && q_g < a.Tq;
-                const float p = live ? __expf(s[r] - m_s[qrow]) * il_s[qrow] : 0.f;
+                float p;
+                if constexpr (MASKED) {
+                    // the row's statistics are read and the exponent is taken whether the key is alive or not, and the result
+                    // is selected: no lane-dependent branch may stand between the dP MFMAs and the first read of their
+                    // accumulator (the compiler counts the wait that read needs through a block which a wave whose lanes are
+                    // all dead skips)
+                    const float e = __expf(s[r] - m_s[qrow]) * il_s[qrow];
+                    p = ((okbits >> r) & 1u) ? e : 0.f;
+                } else {
+                    const bool live = attn_alive<CAUSAL>(kg, klen, q_g) && q_g < a.Tq;
+                    p = live ? __expf(s[r] - m_s[qrow]) * il_s[qrow] : 0.f;
+                }
                 float g = dp[r];
                 float pk = p;
                 if (a.thr != 0u) {
@@ -401,6 +487,74 @@ int ttts_attention_bwd_wide(const float* q, const float* k, const float* v, cons
     a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
     return ATTN_LAUNCH_BWD(attn_wide_bwd_dq_kernel, 0, attn_wide_bwd_dkv_kernel, 0, causal, "attention_bwd_wide", "attn_wide_bwd_dq_kernel",
                            "attn_wide_bwd_dkv_kernel", a, 1, (hipStream_t)stream);
+}
+
+// the mask operands of the _masked entry points: refused before any launch, each refusal naming its value
+static int wide_mask_check(const char* name, const float* add_mask, long ldm, long stride_b, long stride_h, const uint8_t* key_dead,
+                           long ldd, int Tq, int Tk) {
+    TTTS_REQUIRE(add_mask || key_dead, "%s: add_mask and key_dead are both NULL (use the unmasked entry point)", name);
+    if (add_mask) {
+        TTTS_REQUIRE(ldm >= Tk && ldm % 4 == 0, "%s: the mask row stride must be a multiple of 4 floats and >= Tk (ldm %ld, Tk %d)",
+                     name, ldm, Tk);
+        TTTS_REQUIRE(stride_b >= 0 && stride_h >= 0, "%s: mask strides must not be negative (mask_stride_b %ld, mask_stride_h %ld)",
+                     name, stride_b, stride_h);
+        TTTS_REQUIRE(((uintptr_t)add_mask & 15) == 0 && stride_b % 4 == 0 && stride_h % 4 == 0,
+                     "%s: add_mask must be 16-byte aligned in every (batch, head) slice (address %p, mask_stride_b %ld, mask_stride_h %ld)",
+                     name, (const void*)add_mask, stride_b, stride_h);
+        TTTS_REQUIRE((long)Tq * ldm < (1L << 30), "%s: one mask slice exceeds 4 GiB (Tq %d, ldm %ld)", name, Tq, ldm);
+    }
+    TTTS_REQUIRE(!key_dead || ldd >= Tk, "%s: the dead-key row stride must be >= Tk (ldd %ld, Tk %d)", name, ldd, Tk);
+    return TTTS_OK;
+}
+static void wide_mask_fill(AttnMaskArgs& a, const float* add_mask, long ldm, long stride_b, long stride_h, const uint8_t* key_dead, long ldd) {
+    a.add_mask = add_mask; a.key_dead = key_dead;
+    a.mask_stride_b = stride_b; a.mask_stride_h = stride_h;
+    a.ldm = add_mask ? (int)ldm : 4; a.ldd = (int)ldd;
+}
+
+int ttts_attention_fwd_wide_masked(const float* q, const float* k, const float* v, float* o, float* rowstat, float* attn,
+                                   const int64_t* key_lens, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo,
+                                   int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                                   const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
+                                   const uint8_t* key_dead, int64_t ldd, void* stream) {
+    TTTS_REQUIRE(q && k && v && o && rowstat && key_lens, "attention_fwd_wide_masked: null pointer");
+    int rc = attn_check("attention_fwd_wide_masked", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = wide_mask_check("attention_fwd_wide_masked", add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd, Tq, Tk);
+    if (rc) return rc;
+    TTTS_REQUIRE(!(causal && attn), "attention_fwd_wide_masked: the weights are only written by the non-causal (cross) form");
+    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "attention_fwd_wide_masked: q/k/v must be 16-byte aligned");
+    AttnMaskArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    wide_mask_fill(a, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.rowstat = rowstat; a.attn = attn;
+    return attn_launch_fwd("attn_wide_fwd_kernel<masked>", attn_wide_fwd_kernel<true, false, true>, attn_wide_fwd_kernel<false, true, true>,
+                           attn_wide_fwd_kernel<false, false, true>, causal, attn != nullptr, a, (hipStream_t)stream);
+}
+
+int ttts_attention_bwd_wide_masked(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                                   const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
+                                   int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
+                                   int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                                   const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
+                                   const uint8_t* key_dead, int64_t ldd, void* stream) {
+    TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "attention_bwd_wide_masked: null pointer");
+    int rc = attn_check("attention_bwd_wide_masked", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = attn_check_grad_strides("attention_bwd_wide_masked", WHD, H, lddq, lddk, lddv);
+    if (!rc) rc = wide_mask_check("attention_bwd_wide_masked", add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd, Tq, Tk);
+    if (rc) return rc;
+    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
+                 "attention_bwd_wide_masked: q/k/v/o/d_o must be 16-byte aligned");
+    AttnMaskArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    wide_mask_fill(a, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd);
+    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
+    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
+    a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+    const char* names[3] = {"attention_bwd_wide_masked", "attn_wide_bwd_dq_kernel<masked>", "attn_wide_bwd_dkv_kernel<masked>"};
+    return causal ? attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<true, true>, 0, &attn_wide_bwd_dkv_kernel<true, true>, 0>(
+                        names[0], names[1], names[2], a, 1, (hipStream_t)stream)
+                  : attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true>, 0, &attn_wide_bwd_dkv_kernel<false, true>, 0>(
+                        names[0], names[1], names[2], a, 1, (hipStream_t)stream);
 }
 
 }  // extern "C"

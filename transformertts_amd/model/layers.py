@@ -8,15 +8,19 @@ Class names, constructor signatures and parameter names follow the reference's
     device) and the attention kernels derive key-padding and causal masks from them;
     `*_key_padding_mask` / `tgt_mask` / `memory_mask` / `mask` arguments are still accepted: a key-padding mask that is a
     prefix mask becomes lengths and a `tgt_mask` that is the causal mask becomes the kernels' causal flag (one host check per
-    call, only when a mask TENSOR is passed -- the model passes lengths); any other mask keeps its meaning and that attention
-    runs as tensor algebra on library GEMMs (`ops.masked_attention`: correct, not tuned);
+    mask tensor OBJECT, remembered while the tensor lives and is not written to -- the model passes lengths); any other mask
+    keeps its meaning and, at head_dim <= 128, that attention runs on the masked forms of the 128-column kernels (the library's
+    dropout hash and seeds, no score matrix kept); only heads wider than 128 columns run as tensor algebra
+    (`ops.masked_attention`: correct, not tuned);
   * post-norm (`norm_first=False`, the reference's configuration) and pre-norm (`norm_first=True`, the other branch of
     model/layers.py:41-50); batch-first only, relu FFN;
   * residual adds, biases, relu and dropout live in GEMM epilogues, not in separate ops.
 """
 from __future__ import annotations
 
+import collections
 import copy
+import weakref
 from typing import Optional
 
 import torch
@@ -27,6 +31,43 @@ from .. import ops
 
 
 _NEG = torch.finfo(torch.float32).min
+
+
+class _MaskMemo:
+    """What a mask tensor resolves to (lengths, a causal flag, the padded additive form): each answer costs a device read, so it
+    is kept per mask tensor OBJECT -- a weak reference plus the tensor's `_version`, a small LRU.  Never keyed on a storage
+    address: a new tensor at an old address is another object and misses, as does a mask written to in place.  An entry leaves
+    with its mask (the weak reference's callback), so a caller that builds a fresh mask every step pins none of the copies made
+    for earlier ones; no stored value may therefore hold the mask itself.  Under stream capture nothing can be read: an unseen
+    mask raises (run the call once eagerly first, as TrainStep's warm-up steps do)."""
+
+    def __init__(self, size: int = 32):
+        self.size, self.items = size, collections.OrderedDict()
+
+    def _drop(self, key, ref):
+        hit = self.items.get(key)
+        if hit is not None and hit[0] is ref:
+            del self.items[key]
+
+    def get(self, what: tuple, mask: Tensor, compute, valid=None):
+        """`valid`: a further test of a remembered value (it may depend on a second tensor); None = none"""
+        key = (id(mask),) + what
+        hit = self.items.get(key)
+        if hit is not None and hit[0]() is mask and hit[1] == mask._version and (valid is None or valid(hit[2])):
+            self.items.move_to_end(key)
+            return hit[2]
+        if mask.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise ValueError(f"attention mask {tuple(mask.shape)}: resolving a mask reads the device, which a stream capture "
+                             "cannot do; run one eager call with this mask tensor first")
+        value = compute()
+        self.items[key] = (weakref.ref(mask, lambda ref, key=key: self._drop(key, ref)), mask._version, value)
+        self.items.move_to_end(key)
+        while len(self.items) > self.size:
+            self.items.popitem(last=False)
+        return value
+
+
+_memo = _MaskMemo()
 
 
 def _dead_keys(kpm: Tensor) -> Tensor:
@@ -44,15 +85,21 @@ def _dead_keys(kpm: Tensor) -> Tensor:
 
 def _resolve_kpm(kpm: Optional[Tensor], B: int, T: int, device):
     """-> (lengths, dead): a prefix mask (live keys first) is what the kernels derive from lengths -> (lens, None); a mask with
-    holes stays a tensor -> (live-key counts, dead (B, T) bool) and the attention that uses it runs in `ops.masked_attention`."""
+    holes stays a tensor -> (live-key counts, dead (B, T) bool) and the attention that uses it runs on the masked kernels.
+    Remembered per mask tensor (`_MaskMemo`)."""
     if kpm is None:
         return torch.full((B,), T, dtype=torch.int64, device=device), None
     if kpm.dim() != 2 or kpm.shape[0] != B or kpm.shape[1] != T:
         raise ValueError(f"key_padding_mask: expected ({B}, {T}), got {tuple(kpm.shape)}")
-    dead = _dead_keys(kpm)
-    lens = (~dead).sum(dim=1).to(torch.int64)
-    prefix = torch.arange(T, device=dead.device)[None, :] >= lens[:, None]
-    return lens, (None if bool(torch.equal(dead, prefix)) else dead)
+
+    def resolve():
+        dead = _dead_keys(kpm)
+        lens = (~dead).sum(dim=1).to(torch.int64)
+        prefix = torch.arange(T, device=dead.device)[None, :] >= lens[:, None]
+        if bool(torch.equal(dead, prefix)):
+            return lens, None
+        return lens, (dead.clone() if dead is kpm else dead.contiguous())     # (never the mask itself: see _MaskMemo)
+    return _memo.get(("kpm",), kpm, resolve)
 
 
 def _lens_from_kpm(kpm: Optional[Tensor], B: int, T: int, device) -> Tensor:
@@ -66,26 +113,36 @@ def _is_causal_mask(mask: Tensor, Tq: int, Tk: int) -> bool:
     """is `mask` exactly the mask torch's generate_square_subsequent_mask / the reference's model/model.py:251-255 build?"""
     if mask.dim() != 2 or Tq != Tk or mask.shape[0] != Tq or mask.shape[1] != Tk:
         return False
-    ref = torch.triu(torch.ones(Tq, Tk, dtype=torch.bool, device=mask.device), diagonal=1)
-    if mask.dtype == torch.bool:
-        return bool(torch.equal(mask, ref))
-    return bool(torch.equal(torch.isneginf(mask), ref)) and bool((mask.masked_fill(ref, 0) == 0).all())
+
+    def resolve():
+        ref = torch.triu(torch.ones(Tq, Tk, dtype=torch.bool, device=mask.device), diagonal=1)
+        if mask.dtype == torch.bool:
+            return bool(torch.equal(mask, ref))
+        return bool(torch.equal(torch.isneginf(mask), ref)) and bool((mask.masked_fill(ref, 0) == 0).all())
+    return _memo.get(("causal",), mask, resolve)
 
 
 def _additive_mask(mask: Tensor, B: int, H: int, Tq: int, Tk: int) -> Tensor:
     """torch `attn_mask` ((Tq, Tk) or (B * H, Tq, Tk); bool True = not allowed, float = added to the scores) -> finite fp32,
-    broadcastable to (B, H, Tq, Tk)"""
+    broadcastable to (B, H, Tq, Tk), its rows a multiple of 4 floats apart as the masked kernels load them
+    (`ops.pad_mask_rows`).  Remembered per mask tensor (`_MaskMemo`); a float mask that requires grad is differentiated by
+    autograd (`ops.masked_attention`) and is converted on every call."""
     if mask.dim() == 2 and mask.shape[0] == Tq and mask.shape[1] == Tk:
         m = mask[None, None]
     elif mask.dim() == 3 and mask.shape[0] == B * H and mask.shape[1] == Tq and mask.shape[2] == Tk:
         m = mask.reshape(B, H, Tq, Tk)
     else:
         raise ValueError(f"attention mask: expected ({Tq}, {Tk}) or ({B * H}, {Tq}, {Tk}), got {tuple(mask.shape)}")
-    if m.dtype == torch.bool:
-        return torch.zeros(m.shape, dtype=torch.float32, device=m.device).masked_fill(m, _NEG)
-    if bool((torch.isnan(m) | torch.isposinf(m)).any()):
-        raise ValueError("attention mask: float masks may hold finite values and -inf only (NaN / +inf would reach the softmax)")
-    return m.to(torch.float32).clamp_min(_NEG)
+
+    def resolve():
+        if m.dtype == torch.bool:
+            return ops._finite_mask(m)
+        if bool((torch.isnan(m) | torch.isposinf(m)).any()):
+            raise ValueError("attention mask: float masks may hold finite values and -inf only (NaN / +inf would reach the softmax)")
+        return m.to(torch.float32).clamp_min(_NEG)
+    if mask.requires_grad and torch.is_grad_enabled():
+        return resolve()
+    return _memo.get(("additive", B, H), mask, lambda: ops.pad_mask_rows(resolve()) if m.is_cuda else resolve())
 
 
 def _lens_and_kpm(lens: Optional[Tensor], kpm: Optional[Tensor], B: int, T: int, device, what: str):
@@ -95,7 +152,10 @@ def _lens_and_kpm(lens: Optional[Tensor], kpm: Optional[Tensor], B: int, T: int,
         return _resolve_kpm(kpm, B, T, device)
     if kpm is not None:
         got, dead = _resolve_kpm(kpm, B, T, device)
-        if dead is not None or not bool(torch.equal(got.to(lens.device), lens.to(torch.int64).clamp(0, T))):
+
+        def same():       # one device read per (mask, lengths) pair of tensor objects, remembered like the mask's own answers
+            return weakref.ref(lens), lens._version, bool(torch.equal(got.to(lens.device), lens.to(torch.int64).clamp(0, T)))
+        if dead is not None or not _memo.get(("lens", id(lens)), kpm, same, lambda v: v[0]() is lens and v[1] == lens._version)[2]:
             raise ValueError(f"{what}: both lengths and a key-padding mask were given and the mask is not the prefix mask of those "
                              "lengths; pass one of them")
     return lens, None
@@ -104,7 +164,8 @@ def _lens_and_kpm(lens: Optional[Tensor], kpm: Optional[Tensor], B: int, T: int,
 class MultiheadAttention(nn.Module):
     """Parameter layout of nn.MultiheadAttention (packed in-proj, `out_proj` sub-module).  Heads of 64 columns run on the
     head-image kernels, narrower ones on the padded fp32 kernels, heads of 65 .. 128 columns on the 128-column fp32-MFMA kernels
-    (csrc/attention_wide.hip: same masks, dropout sites and seeds), wider ones as tensor algebra (ops.masked_attention)."""
+    (csrc/attention_wide.hip: same masks, dropout sites and seeds), wider ones as tensor algebra (ops.masked_attention).
+    Masks that are tensors (`dead` / `add_mask`) run any head_dim <= 128 on the masked forms of the 128-column kernels."""
 
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0):
         super().__init__()
@@ -132,7 +193,8 @@ class MultiheadAttention(nn.Module):
     def self_attention(self, x: Tensor, lens: Tensor, causal: bool, residual: Tensor, out_drop: float,
                        dead: Optional[Tensor] = None, add_mask: Optional[Tensor] = None) -> Tensor:
         """residual + drop(out_proj(attention(in_proj(x)))); `dead` / `add_mask`: masks the kernels do not derive from lengths
-        (`_resolve_kpm`, `_additive_mask`) -- that attention runs in `ops.masked_attention` between the same two GEMMs"""
+        (`_resolve_kpm`, `_additive_mask`) -- that attention runs on the masked 128-column kernels between the same two GEMMs
+        (`ops.self_attention(..., dead, add_mask)`: the library's dropout site and seed; head_dim > 128: `ops.masked_attention`)"""
         skip = ops.SkipToken() if residual is x else None      # the skip gradient rides in the in-projection's epilogue
         masked = dead is not None or add_mask is not None
         # 64-column heads: q / k / v leave the in-projection as a head image (f16 hi / lo pieces with per-(row, head) scales in the
@@ -140,13 +202,13 @@ class MultiheadAttention(nn.Module):
         img = 3 if (not masked and ops.head_image_ok(x, self.in_proj_weight, self.num_heads, 3)) else 0
         qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias, skip_in=skip, publish_amax=not img, head_image_sections=img)
         p = self._p()
+        on_kernels = not masked or ops.attention_on_kernels(self.embed_dim, self.num_heads, add_mask)
+        seed = ops.seeds.next() if p > 0 and on_kernels else 0       # (the tensor-algebra route draws from torch's generator)
         if masked:
-            d = self.embed_dim
-            ctx, _ = ops.masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, self.num_heads, causal, p,
-                                          dead, add_mask)
+            ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, seed, dead=dead, add_mask=add_mask)
         else:
-            ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, ops.seeds.next() if p > 0 else 0)
-        return self._out(ctx, residual, out_drop, skip, not masked)
+            ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, seed)
+        return self._out(ctx, residual, out_drop, skip, on_kernels)
 
     def cross_attention(self, x: Tensor, mem: Tensor, mem_lens: Tensor, residual: Tensor, out_drop: float,
                         need_weights: bool = True, dead: Optional[Tensor] = None, add_mask: Optional[Tensor] = None, kv=None):
@@ -166,11 +228,13 @@ class MultiheadAttention(nn.Module):
             kv = ops.linear(mem, wkv, ops.param_rows(self.in_proj_bias, d, 3 * d), publish_amax=not img,
                             head_image_sections=2 if img else 0)
         p = self._p()
+        on_kernels = not masked or ops.attention_on_kernels(d, self.num_heads, add_mask)
+        seed = ops.seeds.next() if p > 0 and on_kernels else 0
         if masked:
-            ctx, attn = ops.masked_attention(q, kv[..., :d], kv[..., d:], mem_lens, self.num_heads, False, p, dead, add_mask)
+            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights, dead=dead, add_mask=add_mask)
         else:
-            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, ops.seeds.next() if p > 0 else 0, need_weights)
-        return self._out(ctx, residual, out_drop, skip, not masked), (attn if need_weights else None)
+            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights)
+        return self._out(ctx, residual, out_drop, skip, on_kernels), (attn if need_weights else None)
 
 
 def _ffn_block(layer, x: Tensor, out_dropout: nn.Dropout, residual: Optional[Tensor] = None) -> Tensor:

@@ -1838,6 +1838,85 @@ def _attn_wide_bwd(*args) -> None:
     _lib.check(_lib.load().ttts_attention_bwd_wide(*args, _stream()), "ttts_attention_bwd_wide")
 
 
+def _attn_wide_masked_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_scale: float, mask):
+    """`_attn_wide_fwd` under tensor masks; `mask`: the six mask arguments of the C ABI (`_mask_args`)."""
+    dev = lens.device
+    o = torch.empty(B, Tq, H * 128, dtype=torch.float32, device=dev)
+    stat = torch.empty(2, B, H, Tq, dtype=torch.float32, device=dev)
+    attn = torch.empty(B, H, Tq, Tk, dtype=torch.float32, device=dev) if need_weights else None
+    _lib.check(_lib.load().ttts_attention_fwd_wide_masked(q, k, v, _p(o), _p(stat), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv,
+                                                          H * 128, 1 if causal else 0, float(q_scale), float(drop_p), seed,
+                                                          _ss(), *mask, _stream()), "ttts_attention_fwd_wide_masked")
+    return o, stat, attn
+
+
+def _attn_wide_masked_bwd(*args) -> None:
+    """Backward of `_attn_wide_masked_fwd`; `args` = every C-ABI argument up to ldd."""
+    _lib.check(_lib.load().ttts_attention_bwd_wide_masked(*args, _stream()), "ttts_attention_bwd_wide_masked")
+
+
+def mask_row_stride(Tk: int) -> int:
+    """row stride (floats) of an additive mask as the kernels load it: 16-byte quads, so a multiple of 4"""
+    return (Tk + 3) // 4 * 4
+
+
+def pad_mask_rows(m: torch.Tensor) -> torch.Tensor:
+    """(..., Tq, Tk) fp32 -> the same values as a (..., Tq, Tk) view of a zero-padded (..., Tq, mask_row_stride(Tk)) buffer"""
+    Tk = m.shape[-1]
+    buf = torch.zeros(*m.shape[:-1], mask_row_stride(Tk), dtype=torch.float32, device=m.device)
+    buf[..., :Tk] = m
+    return buf[..., :Tk]
+
+
+def _mask_operand(add_mask: torch.Tensor, B: int, H: int, Tq: int, Tk: int) -> torch.Tensor:
+    """An additive mask -- (Tq, Tk), (B*H, Tq, Tk) or (B | 1, H | 1, Tq, Tk); bool (True = not allowed) or float (added to the
+    scores; -inf and anything at or below half the lowest finite float forbid the key) -- as the 4-D fp32 tensor the kernels
+    address: unit column stride, rows a multiple of 4 floats apart, every (batch, head) slice 16-byte aligned, broadcast
+    dimensions with stride 0.  Used in place when it already is that (`pad_mask_rows` makes one), copied otherwise."""
+    m = add_mask
+    if m.dim() == 2:
+        m = m[None, None]
+    elif m.dim() == 3:
+        if m.shape[0] != B * H:
+            raise ValueError(f"attention mask: expected ({B * H}, {Tq}, {Tk}), got {tuple(add_mask.shape)}")
+        m = m.reshape(B, H, Tq, Tk)
+    if m.dim() != 4 or m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] != Tq or m.shape[3] != Tk:
+        raise ValueError(f"attention mask: expected ({Tq}, {Tk}), ({B * H}, {Tq}, {Tk}) or (B | 1, H | 1, {Tq}, {Tk}), got "
+                         f"{tuple(add_mask.shape)}")
+    if not m.is_cuda:
+        raise ValueError(f"attention mask: expected a CUDA/HIP tensor (the HIP path has no CPU fallback), got {m.device}")
+    if m.dtype == torch.bool:
+        m = _finite_mask(m)
+    elif m.dtype != torch.float32:
+        m = m.to(torch.float32)
+    sb, sh, sr, sc = m.stride()
+    if m.shape[0] == 1:
+        sb = 0
+    if m.shape[1] == 1:
+        sh = 0
+    ok = (sc == 1 or Tk == 1) and (sr % 4 == 0 and sr >= Tk or Tq == 1) and sb % 4 == 0 and sh % 4 == 0 and sb >= 0 and sh >= 0 \
+        and m.data_ptr() % 16 == 0
+    if ok:      # the kernels address whole rows of every slice (Tq rows of `ldm` floats): they must lie inside the storage
+        ldm = sr if Tq > 1 else mask_row_stride(Tk)
+        end = m.storage_offset() + sb * (m.shape[0] - 1) + sh * (m.shape[1] - 1) + Tq * ldm
+        ok = end * 4 <= m.untyped_storage().nbytes()
+    if not ok:
+        m = pad_mask_rows(m)
+    return m
+
+
+def _mask_args(dead: Optional[torch.Tensor], mask4: Optional[torch.Tensor], Tk: int):
+    """(add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd) of the masked C entry points; mask4: `_mask_operand`'s"""
+    if mask4 is None:
+        mk = (None, 0, 0, 0)
+    else:
+        ldm = mask4.stride(2) if mask4.shape[2] > 1 else mask_row_stride(Tk)
+        if mask4.shape[2] == 1 and mask4.shape[3] > 1 and mask4.stride(3) != 1:
+            raise ValueError("attention mask: columns must be contiguous")
+        mk = (_p(mask4), ldm, mask4.stride(0) if mask4.shape[0] > 1 else 0, mask4.stride(1) if mask4.shape[1] > 1 else 0)
+    return (*mk, _p(dead), 0 if dead is None else dead.stride(0))
+
+
 def _off(t: torch.Tensor, col: int):
     return c_void_p(t.data_ptr() + 4 * col)
 
@@ -1889,8 +1968,10 @@ def masked_attention(q, k, v, lens, n_head: int, causal: bool, drop_p: float, de
     hand-written kernels do not take:
       * heads wider than 128 columns (the reference takes any `nhead`, model/model.py:139-161; no BASELINE configuration has
         them): the kernels hold a head of at most 128 columns per lane;
-      * masks that are not "keys past a length" / causal (a key-padding mask with holes, `memory_mask`, an arbitrary `tgt_mask` /
-        `mask` -- arguments of the reference's layers, model/layers.py:29-74, that its model never passes).
+      * a float mask that requires grad: autograd differentiates it here, the kernels give no gradient of a mask.
+    Masks that are tensors (a key-padding mask with holes, `memory_mask`, an arbitrary `tgt_mask` / `mask` -- arguments of the
+    reference's layers, model/layers.py:29-74) run on the masked 128-column kernels otherwise (`self_attention` /
+    `cross_attention` with `dead` / `add_mask`); this function is also what tests and tools/attn_bench.py compare them with.
     Same conventions as the kernels (weights returned AFTER dropout, rows without an allowed key give zeros), differentiated by
     autograd.  `dead` (B, Tk) bool replaces the keys-past-`lens` mask; `add_mask` (broadcastable to (B, H, Tq, Tk), finite) is
     added to the scaled scores as torch adds a float `attn_mask`.  Correct, not tuned."""
@@ -2101,10 +2182,18 @@ class AttentionFn(torch.autograd.Function):
     (heads of 64 are read in place, narrower ones through zero-padded copies).  64 < head_dim <= 128: the fp32-MFMA kernels on
     128-column heads (csrc/attention_wide.hip; 128 in place, narrower through copies padded to 128), which take no operand
     maxima and publish none.  Saved for backward at either width: the operands, o, the row statistics, the lengths and the
-    padded copies -- never the weights."""
+    padded copies -- never the weights.
+    `dead` ((B, Tk) bool, True = key not attended to; REPLACES the keys-past-`lens` mask as in `masked_attention`) and / or
+    `add_mask` (see `_mask_operand`; no gradient): masks that are tensors.  Any head_dim <= 128 then runs on the MASKED forms
+    of the 128-column kernels (narrower heads padded to 128), and the two mask tensors are saved too -- nothing else of size
+    (Tq, Tk), with one exception: an `add_mask` the kernels cannot address in place (bool, another dtype, a row stride that is no
+    multiple of 4 floats, a misaligned slice) is copied by `_mask_operand` and the COPY is saved -- for a per-(batch, head) mask
+    that is one score matrix.  `pad_mask_rows` makes a mask that is used in place (the layers pass such a one).  No host read,
+    nothing from torch's generator: the call captures into a HIP graph."""
 
     @staticmethod
-    def forward(ctx, q, kv, lens, n_head, causal, drop_p, seed, need_weights, q_amax=None, kv_amax=None, o_amax=None):
+    def forward(ctx, q, kv, lens, n_head, causal, drop_p, seed, need_weights, q_amax=None, kv_amax=None, o_amax=None,
+                dead=None, add_mask=None):
         q = _chk(q, "attention.q")
         kv = _chk(kv, "attention.kv") if kv is not None else None
         lens = _chk(lens, "attention.lens", torch.int64)
@@ -2113,7 +2202,20 @@ class AttentionFn(torch.autograd.Function):
         hd = _head_width(d, n_head)
         if hd > 128:
             raise ValueError(f"attention kernels take head_dim <= 128 (d_model {d}, heads {n_head}: head_dim {hd})")
-        W = 64 if hd <= 64 else 128      # columns per head as the kernels see them
+        masked = dead is not None or add_mask is not None
+        mask4 = None
+        if masked:
+            if dead is not None:
+                dead = _chk(dead, "attention.dead", torch.bool)
+                if tuple(dead.shape) != (B, Tk):
+                    raise ValueError(f"attention.dead: expected ({B}, {Tk}), got {tuple(dead.shape)}")
+                # one past the last live key per utterance: the stages behind it are skipped
+                lens = (torch.arange(1, Tk + 1, device=dead.device) * ~dead).amax(dim=1)
+            if add_mask is not None:
+                if add_mask.requires_grad:
+                    raise ValueError("attention: the kernels give no gradient of a mask (ops.masked_attention does)")
+                mask4 = _mask_operand(add_mask, B, n_head, Tq, Tk)
+        W = 128 if masked or hd > 64 else 64      # columns per head as the kernels see them
         if W == 128:
             q_amax = kv_amax = None      # exact fp32 products: no pre-scales
         else:
@@ -2127,7 +2229,10 @@ class AttentionFn(torch.autograd.Function):
         else:
             pads = tuple(_pad_heads(t, c, ld, B * t.shape[1], n_head, hd, W) for t, c, ld in wins)
             ptrs, lds = [_p(t) for t in pads], [n_head * W] * 3
-        if W == 128:
+        if masked:
+            o64, stat, attn = _attn_wide_masked_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights,
+                                                    hd ** -0.5, _mask_args(dead, mask4, Tk))
+        elif W == 128:
             o64, stat, attn = _attn_wide_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, hd ** -0.5)
         else:
             o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_amax,
@@ -2138,9 +2243,9 @@ class AttentionFn(torch.autograd.Function):
         else:
             o = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
             _unpad_heads(o64, o, 0, d, B * Tq, n_head, hd, W)
-        ctx.save_for_backward(q, kv, o64, stat, lens, *pads)
+        ctx.save_for_backward(q, kv, o64, stat, lens, dead, mask4, *pads)
         ctx.amax = (q_amax, kv_amax)
-        ctx.cfg = (n_head, causal, float(drop_p), seed, hd)
+        ctx.cfg = (n_head, causal, float(drop_p), seed, hd, W)
         ctx.ss = _ss()
         if attn is None:       # weights not requested: single-pass online softmax, nothing written
             attn = torch.empty(0, dtype=torch.float32, device=q.device)
@@ -2151,11 +2256,11 @@ class AttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do, _dattn):
         if do is None:
-            return (None,) * 11
+            return (None,) * 13
         lib = _lib.load()
-        q, kv, o64, stat, lens, *pads = ctx.saved_tensors
-        n_head, causal, drop_p, seed, hd = ctx.cfg
-        W = 64 if hd <= 64 else 128
+        q, kv, o64, stat, lens, dead, mask4, *pads = ctx.saved_tensors
+        n_head, causal, drop_p, seed, hd, W = ctx.cfg
+        masked = dead is not None or mask4 is not None
         do = _chk(do, "attention.do")
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv) if kv is not None else None
@@ -2172,8 +2277,12 @@ class AttentionFn(torch.autograd.Function):
             grads = [torch.empty(B * t.shape[1], n_head * W, dtype=torch.float32, device=q.device) for t, _, _ in gwins]
             outs, ldg = [_p(t) for t in grads], [n_head * W] * 3
         if W == 128:
-            _attn_wide_bwd(*ins, _p(o64), _p(do64), _p(stat), _p(delta), *outs, _p(lens), B, n_head, Tq, Tk, *lds, n_head * W,
-                           *ldg, 1 if causal else 0, hd ** -0.5, drop_p, seed, ctx.ss)
+            args = (*ins, _p(o64), _p(do64), _p(stat), _p(delta), *outs, _p(lens), B, n_head, Tq, Tk, *lds, n_head * W, *ldg,
+                    1 if causal else 0, hd ** -0.5, drop_p, seed, ctx.ss)
+            if masked:
+                _attn_wide_masked_bwd(*args, *_mask_args(dead, mask4, Tk))
+            else:
+                _attn_wide_bwd(*args)
         else:
             lse, rowstat = stat[0], stat[1:]
             # max|dq|, max|dk, dv| for the in-projection gradients: ONE array for the one gradient of a packed projection
@@ -2189,15 +2298,43 @@ class AttentionFn(torch.autograd.Function):
         if hd != W:
             for g, (t, c, ld) in zip(grads, gwins):
                 _unpad_heads(g, t, c, ld, g.shape[0], n_head, hd, W)
-        return dq, dkv, None, None, None, None, None, None, None, None, None
+        return dq, dkv, None, None, None, None, None, None, None, None, None, None, None
 
 
-def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: int):
+def _mask_needs_autograd(add_mask) -> bool:
+    return add_mask is not None and add_mask.requires_grad and torch.is_grad_enabled()
+
+
+def _finite_mask(add_mask):
+    """an additive mask as `masked_attention` takes it: float and finite (bool True / -inf -> the lowest finite float)"""
+    if add_mask is None:
+        return None
+    big = torch.finfo(torch.float32).min
+    if add_mask.dtype == torch.bool:
+        return torch.zeros(add_mask.shape, dtype=torch.float32, device=add_mask.device).masked_fill(add_mask, big)
+    return add_mask.clamp_min(big)
+
+
+def attention_on_kernels(d: int, n_head: int, add_mask=None) -> bool:
+    """does `self_attention` / `cross_attention` run this configuration on the attention kernels (else: `masked_attention`)"""
+    return _head_width(d, n_head) <= 128 and not _mask_needs_autograd(add_mask)
+
+
+def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: int, dead=None, add_mask=None):
     """Self-attention over a packed in-projection output (a Tensor, or the HeadImage `linear(..., head_image_sections=3)`
     returned); the partial maxima of a fp32 `qkv` ride on it when its producer left them (`linear(..., publish_amax=True)`), and
-    the context leaves with its own for the out-projection."""
+    the context leaves with its own for the out-projection.
+    `dead` / `add_mask` (see AttentionFn): masks that are tensors; fp32 operands and head_dim <= 128 run on the masked 128-column
+    kernels.  Wider heads and a float mask that requires grad go to `masked_attention` (torch's generator draws their dropout)."""
     d = qkv.shape[-1] // 3
     hd = _head_width(d, n_head)
+    if dead is not None or add_mask is not None:
+        if isinstance(qkv, HeadImage) or _twin(qkv) is not None:
+            raise ValueError("self_attention: a head image / twin batch takes length masks only")
+        if hd > 128 or _mask_needs_autograd(add_mask):
+            return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p, dead,
+                                    _finite_mask(add_mask))[0]
+        return AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False, None, None, None, dead, add_mask)[0]
     if hd > 64:
         if isinstance(qkv, HeadImage):
             raise ValueError("self_attention: head images hold 64-column heads")
@@ -2222,10 +2359,18 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
     return o
 
 
-def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_weights: bool = True):
-    """q (B,Tq,d), kv (B,Tk,2d): both fp32 tensors, or both HeadImages (kv may be one layer's window of `cross_kv_projection`)"""
+def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_weights: bool = True, dead=None, add_mask=None):
+    """q (B,Tq,d), kv (B,Tk,2d): both fp32 tensors, or both HeadImages (kv may be one layer's window of `cross_kv_projection`).
+    `dead` / `add_mask`: as in `self_attention`."""
     d = q.shape[-1]
     hd = _head_width(d, n_head)
+    if dead is not None or add_mask is not None:
+        if isinstance(q, HeadImage) or isinstance(kv, HeadImage) or _twin(q) is not None:
+            raise ValueError("cross_attention: a head image / twin batch takes length masks only")
+        if hd > 128 or _mask_needs_autograd(add_mask):
+            o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p, dead, _finite_mask(add_mask))
+            return o, (attn if need_weights else None)
+        return AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights, None, None, None, dead, add_mask)
     if hd > 64:
         if isinstance(q, HeadImage) or isinstance(kv, HeadImage):
             raise ValueError("cross_attention: head images hold 64-column heads")
