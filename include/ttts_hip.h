@@ -460,6 +460,45 @@ int ttts_attention_bwd_wide_masked(const float* q, const float* k, const float* 
                                    int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
                                    const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
                                    const uint8_t* key_dead, int64_t ldd, void* stream);
+/* ---- the 128-column attention backward when the returned weights carry a gradient of their own (ABI v19; attention_wide.hip
+ * DATTN forms): the decoder's `_mha_block` hands out the per-head post-dropout weights of nn.MultiheadAttention(need_weights=True,
+ * average_attn_weights=False) (model/layers.py:68-74) as ordinary autograd tensors, so a loss written on output['alignments']
+ * reaches q, k and v through softmax and dropout (torch/nn/functional.py:6578-6610: baddbmm -> softmax -> dropout -> bmm).
+ * Arguments of ttts_attention_bwd_wide_masked -- add_mask and key_dead may BOTH be NULL here -- plus:
+ *   attn     the (B,H,Tq,Tk) weights A the forward wrote for these operands, masks, drop_p, seed and step word, contiguous
+ *   d_attn   fp32: element (b, h, q, key) at d_attn[b*dattn_stride_b + h*dattn_stride_h + q*ld_dattn + key] (strides in
+ *            elements, 0 = broadcast); ld_dattn a multiple of 4 floats and >= Tk, every slice 16-byte aligned and below 4 GiB.
+ *            Elements of keys that are not alive are never used.
+ * With P the softmax over the alive keys, D the keep mask and A = D o P / (1 - p): dS = P o (D / (1 - p) (d_o . v + d_attn) -
+ * delta), delta = d_o . o + sum_n A d_attn (the sum in a fixed order per row); dV is that of the _wide entry points; the
+ * one-hot rule stands.  Non-causal only.  Refused before any launch, naming the value: NULL attn or d_attn, causal != 0,
+ * ld_dattn < Tk or no multiple of 4, a misaligned slice, negative strides, a slice over 4 GiB, and what the _masked entry point
+ * refuses of a mask that is given. */
+int ttts_attention_bwd_wide_dattn(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                                  const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
+                                  int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
+                                  int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                                  const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
+                                  const uint8_t* key_dead, int64_t ldd, const float* attn, const float* d_attn, int64_t ld_dattn,
+                                  int64_t dattn_stride_b, int64_t dattn_stride_h, void* stream);
+/* ---- guided attention loss on the alignment maps (ABI v19; guided.hip): the term Transformer-TTS recipes add on
+ * output['alignments'] (the per-head weights of model/layers.py:68-74, a list with one (B,H,Tm,Tp) map per decoder layer,
+ * model/model.py) -- in torch, per selected map, `(attn * W[:, None]).sum()` over a host-built (B,Tm,Tp) prior
+ *   W_b[t][n] = 1 - exp(-(n / N_b - t / T_b)^2 / (2 sigma^2)) for t < T_b = melspec_lens[b], n < N_b = phoneme_lens[b], else 0,
+ * summed over the maps and divided by n_selected * sum_b T_b N_b (n_selected = selected maps x selected heads).  Forward: one call
+ * per selected map writes its B*H*Tm row sums to partials[map_index] (partials: (n_maps, B*H*Tm) floats; head_mask: 0 = every
+ * head, else bit h = head h counts, H <= 64); the call with loss_out != NULL (the last one) also sums all n_maps * B*H*Tm partials
+ * in a fixed order and writes the scalar.  Backward: reads the upstream gradient *g_loss from device memory and writes
+ * d_attn[plane][t][n] = g W_b[t][n] / (n_selected sum T N) with row stride ld (a multiple of 4 floats, >= Tp) and exact zeros in
+ * padding rows and columns: (B, Tm, ld) when head_mask is 0 -- one tensor that serves every selected map and, through a head
+ * stride of 0, every head (ttts_attention_bwd_wide_dattn) -- else (B, H, Tm, ld) with zero planes for unselected heads.  The
+ * normaliser is formed on the device; nothing is read back, no atomics: both calls capture into a HIP graph and repeat bit for
+ * bit.  Refused, naming the value: sigma <= 0, non-positive sizes or n_selected, a head_mask bit past H, a bad ld or map_index. */
+int ttts_guided_attention_fwd(const float* attn, const int64_t* phoneme_lens, const int64_t* melspec_lens, uint64_t head_mask,
+                              float sigma, int B, int H, int Tm, int Tp, float* partials, int map_index, int n_maps, int n_selected,
+                              float* loss_out, void* stream);
+int ttts_guided_attention_bwd(const float* g_loss, const int64_t* phoneme_lens, const int64_t* melspec_lens, uint64_t head_mask,
+                              float sigma, int n_selected, int B, int H, int Tm, int Tp, int ld, float* d_attn, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -88,6 +88,10 @@ SIGNATURES = {
     "ttts_attention_fwd_wide_masked": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U, P, P, L, L, L, P, L, P]),
     "ttts_attention_bwd_wide_masked": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, P, L, L, L,
                                            P, L, P]),
+    "ttts_attention_bwd_wide_dattn": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, P, L, L, L,
+                                          P, L, P, P, L, L, L, P]),
+    "ttts_guided_attention_fwd": (I, [P, P, P, U, F, I, I, I, I, P, I, I, I, P, P]),
+    "ttts_guided_attention_bwd": (I, [P, P, P, U, F, I, I, I, I, I, I, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

@@ -230,6 +230,20 @@ __device__ __forceinline__ uint32_t dead_tile_bits(__amdgpu_buffer_rsrc_t rsrc, 
     return (uint32_t)__ballot(dead_load(rsrc, key0 + l31)) >> (4 * half);
 }
 
+// ---- a gradient of the written weights (the DATTN forms of the 128-column backward kernels): fp32, addressed like the additive
+// mask -- element (b, h, q, key) at d_attn[b*dattn_stride_b + h*dattn_stride_h + q*ld_dattn + key], strides in elements, 0 =
+// broadcast, ld_dattn a multiple of 4 floats, every slice 16-byte aligned -- and read with the mask's loads (mask_load_row16 /
+// mask_load_col16) through a descriptor over the slice's Tq rows.  What is read for a key that is not alive (columns past Tk,
+// the neighbouring row) is never used: the kernels select on the key's liveness.  `attn`: the forward's own (B,H,Tq,Tk) weights.
+struct AttnDattnArgs : AttnMaskArgs {
+    const float* attn_w; const float* d_attn;
+    long dattn_stride_b, dattn_stride_h;
+    int ld_dattn;
+};
+__device__ __forceinline__ RowSrc dattn_src(const AttnDattnArgs& a, int b, int h) {
+    return row_src(a.d_attn + b * a.dattn_stride_b + h * a.dattn_stride_h, a.Tq, a.ld_dattn);
+}
+
 // ---- dropout of a lane's weights: registers r .. r+3 of a lane are four neighbouring keys and share one hash word `qh` (of
 // the quad of `key`); SCALE: the kept ones are multiplied by 1/(1-p) here (else that factor rides in a later scale)
 template <bool SCALE>

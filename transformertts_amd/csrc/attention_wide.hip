@@ -46,6 +46,10 @@ __device__ __forceinline__ void wide_dot(const float* tile, int l31, int half, c
 // attn_alive_masked.  The mask loads are issued with the stage's operand loads; a row that no key is left for gives zeros like
 // an utterance without keys.
 template <bool MASKED> using WideArgs = std::conditional_t<MASKED, AttnMaskArgs, AttnArgs>;
+// DATTN (backward kernels, non-causal MASKED forms only): the weights the forward wrote have a gradient dA of their own
+// (AttnDattnArgs).  With A = D o P / (1 - p) as written: dA_tot = dO . V + dA, dS = P o (D / (1 - p) dA_tot - delta),
+// delta = dO . O + sum_n A dA.  The second term of delta is in `a.delta` when the dQ kernel starts (attn_dattn_rowdot_kernel).
+template <bool MASKED, bool DATTN> using WideBwdArgs = std::conditional_t<DATTN, AttnDattnArgs, WideArgs<MASKED>>;
 
 template <bool CAUSAL, bool WRITE_A, bool MASKED = false>
 __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(WideArgs<MASKED> a) {
@@ -217,8 +221,25 @@ __global__ __launch_bounds__(256, 2) void attn_wide_fwd_kernel(WideArgs<MASKED> 
 }
 
 // =====================================================================================  backward: dQ (+ delta)
-template <bool CAUSAL, bool MASKED = false>
-__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKED> a) {
+// delta[row] = sum_n A[row][n] dA[row][n] over the Tk keys of one (b, h, q) row: one wave per row, lane j takes keys j, j + 64,
+// ... in ascending order and the 64 partial sums meet in a fixed xor tree -- the same bits whatever the grid or arrival order
+__global__ __launch_bounds__(256) void attn_dattn_rowdot_kernel(const float* attn, const float* d_attn, long stride_b, long stride_h,
+                                                                int ld, float* delta, int H, int Tq, int Tk, long rows) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const long t = row % Tq, bh = row / Tq;
+    const float* ar = attn + row * Tk;
+    const float* gr = d_attn + (bh / H) * stride_b + (bh % H) * stride_h + t * ld;
+    float acc = 0.f;
+    for (int n = lane; n < Tk; n += 64) acc = fmaf(ar[n], gr[n], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) delta[row] = acc;
+}
+
+template <bool CAUSAL, bool MASKED = false, bool DATTN = false>
+__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideBwdArgs<MASKED, DATTN> a) {
+    static_assert(!DATTN || (MASKED && !CAUSAL), "the weights are written by the non-causal form only; DATTN rides on MASKED");
     const uint64_t seed_eff = site_seed(a.seed, a.step_seed);
     const uint32_t thr16 = a.thr << 16;
     __shared__ __attribute__((aligned(16))) float smem[WSMEM_FLOATS];
@@ -257,6 +278,7 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKE
         }
     }
     delta += __shfl_xor(delta, 32, 64);
+    if constexpr (DATTN) delta += (qg < a.Tq) ? a.delta[arow + qg] : 0.f;      // sum_n A dA of the row (attn_dattn_rowdot_kernel)
     if (half == 0 && qg < a.Tq) a.delta[arow + qg] = delta;
     const float m_q = (qg < a.Tq) ? a.rowstat[arow + qg] : 0.f;
     const float l_q = (qg < a.Tq) ? a.rowstat[(long)a.B * a.H * a.Tq + arow + qg] : 0.f;
@@ -274,6 +296,10 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKE
     RowSrc msrc;
     __amdgpu_buffer_rsrc_t dsrc;
     if constexpr (MASKED) { msrc = mask_src(a, b, h); dsrc = dead_src(a, b); }
+    // DATTN: the lane's 16 values of its dA row of the stage in flight, loaded like the mask row
+    float da[DATTN ? 16 : 1];
+    RowSrc gsrc;
+    if constexpr (DATTN) gsrc = dattn_src(a, b, h);
 
     for (int t = 0; t < kr.nst; ++t) {
         __syncthreads();
@@ -281,6 +307,7 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKE
             mask_load_row16(msrc, qg, t * WKB, half, mk);
             dbits = dead_tile_bits(dsrc, t * WKB, l31, half);
         }
+        if constexpr (DATTN) mask_load_row16(gsrc, qg, t * WKB, half, da);
         stage_rows<WHD, true>(kb_, (long)t * WKB, a.Tk, a.ldk, tid, Ks, 1.f);
         stage_rows<WHD, true>(vb_, (long)t * WKB, a.Tk, a.ldv, tid, Vs, 1.f);
         __syncthreads();
@@ -308,6 +335,10 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKE
                     else
                         p = attn_alive<CAUSAL>(kg, klen, qg) ? __expf(s[r + e] - m_q) * inv_l : 0.f;
                     float g = dp[r + e];
+                    // DATTN: dA of a key that is not alive is whatever lies there; selected, not branched on (straight-line code
+                    // from the dP MFMAs to the first read of their accumulator)
+                    if constexpr (DATTN)
+                        g += attn_alive_masked<CAUSAL>(kg, klen, qg, (dbits >> acc_row(r + e, 0)) & 1u, mk[r + e]) ? da[r + e] : 0.f;
                     if (MASKED || a.thr != 0u) g = attn_drop1<true>(g, qh, e, thr16, a.drop_scale);
                     ds[r + e] = one_hot ? 0.f : p * (g - delta);
                 }
@@ -326,8 +357,9 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dq_kernel(WideArgs<MASKE
 }
 
 // =====================================================================================  backward: dK, dV
-template <bool CAUSAL, bool MASKED = false>
-__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideArgs<MASKED> a) {
+template <bool CAUSAL, bool MASKED = false, bool DATTN = false>
+__global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideBwdArgs<MASKED, DATTN> a) {
+    static_assert(!DATTN || (MASKED && !CAUSAL), "the weights are written by the non-causal form only; DATTN rides on MASKED");
     const uint64_t seed_eff = site_seed(a.seed, a.step_seed);
     const uint32_t thr16 = a.thr << 16;
     __shared__ __attribute__((aligned(16))) float smem[WSMEM_FLOATS];
@@ -372,6 +404,15 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideArgs<MASK
     bool kdead = false;
     RowSrc msrc;
     if constexpr (MASKED) { msrc = mask_src(a, b, h); kdead = dead_load(dead_src(a, b), kg); }
+    // DATTN: the lane's dA column arrives and waits the same way, in a further lane-private column of WIDE_DATTN_LDS bytes of
+    // dynamic LDS (with it the kernel holds more than 64 KB: the launch opts in, attn_launch_bwd_pair)
+    float* dacol = nullptr;
+    RowSrc gsrc;
+    if constexpr (DATTN) {
+        extern __shared__ float dattn_s[];
+        dacol = dattn_s + wave * 16 * 64 + lane;
+        gsrc = dattn_src(a, b, h);
+    }
 
     for (int qs = qs_begin; qs < nqs; ++qs) {
         __syncthreads();
@@ -382,6 +423,12 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideArgs<MASK
             mask_load_col16(msrc, qs * WKB, kg, half, mk);
 #pragma unroll
             for (int r = 0; r < 16; ++r) mcol[r * 64] = mk[r];
+        }
+        if constexpr (DATTN) {
+            float dav[16];
+            mask_load_col16(gsrc, qs * WKB, kg, half, dav);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dacol[r * 64] = dav[r];
         }
         if (tid < WKB) {
             const int q = qs * WKB + tid;
@@ -425,6 +472,7 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideArgs<MASK
                     p = live ? __expf(s[r] - m_s[qrow]) * il_s[qrow] : 0.f;
                 }
                 float g = dp[r];
+                if constexpr (DATTN) g += ((okbits >> r) & 1u) ? dacol[r * 64] : 0.f;
                 float pk = p;
                 if (a.thr != 0u) {
                     const bool keep = attn_keep(seed_eff, (uint32_t)(arow + q_g), (uint32_t)kg, thr16);
@@ -453,6 +501,8 @@ __global__ __launch_bounds__(256, 1) void attn_wide_bwd_dkv_kernel(WideArgs<MASK
 }  // namespace ttts
 
 using namespace ttts;
+
+constexpr int WIDE_DATTN_LDS = 4 * 16 * 64 * 4;      // the dA columns of the DATTN dK/dV kernel: 16 floats per lane, dynamic LDS
 
 extern "C" {
 
@@ -555,6 +605,56 @@ int ttts_attention_bwd_wide_masked(const float* q, const float* k, const float* 
                         names[0], names[1], names[2], a, 1, (hipStream_t)stream)
                   : attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true>, 0, &attn_wide_bwd_dkv_kernel<false, true>, 0>(
                         names[0], names[1], names[2], a, 1, (hipStream_t)stream);
+}
+
+// the gradient of the weights of ttts_attention_bwd_wide_dattn: refused before any launch, each refusal naming its value
+static int wide_dattn_check(const char* name, const float* attn, const float* d_attn, long ld, long stride_b, long stride_h, int causal,
+                            int Tq, int Tk) {
+    TTTS_REQUIRE(attn, "%s: attn is NULL (the forward's weights are required)", name);
+    TTTS_REQUIRE(d_attn, "%s: d_attn is NULL (use ttts_attention_bwd_wide / _masked without a gradient of the weights)", name);
+    TTTS_REQUIRE(!causal, "%s: the weights are only written by the non-causal (cross) form (causal %d)", name, causal);
+    TTTS_REQUIRE(ld >= Tk && ld % 4 == 0, "%s: the d_attn row stride must be a multiple of 4 floats and >= Tk (ld_dattn %ld, Tk %d)",
+                 name, ld, Tk);
+    TTTS_REQUIRE(stride_b >= 0 && stride_h >= 0, "%s: d_attn strides must not be negative (dattn_stride_b %ld, dattn_stride_h %ld)",
+                 name, stride_b, stride_h);
+    TTTS_REQUIRE(((uintptr_t)d_attn & 15) == 0 && stride_b % 4 == 0 && stride_h % 4 == 0,
+                 "%s: d_attn must be 16-byte aligned in every (batch, head) slice (address %p, dattn_stride_b %ld, dattn_stride_h %ld)",
+                 name, (const void*)d_attn, stride_b, stride_h);
+    TTTS_REQUIRE((long)Tq * ld < (1L << 30), "%s: one d_attn slice exceeds 4 GiB (Tq %d, ld_dattn %ld)", name, Tq, ld);
+    return TTTS_OK;
+}
+
+int ttts_attention_bwd_wide_dattn(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                                  const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
+                                  int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
+                                  int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                                  const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
+                                  const uint8_t* key_dead, int64_t ldd, const float* attn, const float* d_attn, int64_t ld_dattn,
+                                  int64_t dattn_stride_b, int64_t dattn_stride_h, void* stream) {
+    const char* entry = "attention_bwd_wide_dattn";
+    TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "%s: null pointer", entry);
+    int rc = attn_check(entry, WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = attn_check_grad_strides(entry, WHD, H, lddq, lddk, lddv);
+    if (!rc) rc = wide_dattn_check(entry, attn, d_attn, ld_dattn, dattn_stride_b, dattn_stride_h, causal, Tq, Tk);
+    if (!rc && (add_mask || key_dead)) rc = wide_mask_check(entry, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd, Tq, Tk);
+    if (rc) return rc;
+    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
+                 "%s: q/k/v/o/d_o must be 16-byte aligned", entry);
+    AttnDattnArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    wide_mask_fill(a, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd);      // both NULL: empty descriptors, s + 0.f == s
+    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
+    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
+    a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+    a.attn_w = attn; a.d_attn = d_attn; a.ld_dattn = (int)ld_dattn;
+    a.dattn_stride_b = dattn_stride_b; a.dattn_stride_h = dattn_stride_h;
+    const long rows = (long)B * H * Tq;
+    TTTS_REQUIRE(rows < (1L << 32), "%s: grid too large (B*H*Tq %ld)", entry, rows);
+    hipLaunchKernelGGL(attn_dattn_rowdot_kernel, dim3((unsigned)cdiv(rows, 4L)), dim3(256), 0, (hipStream_t)stream, attn, d_attn,
+                       (long)dattn_stride_b, (long)dattn_stride_h, (int)ld_dattn, delta, H, Tq, Tk, rows);
+    TTTS_LAUNCH_CHECK("attn_dattn_rowdot_kernel");
+    return attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true, true>, 0, &attn_wide_bwd_dkv_kernel<false, true, true>, WIDE_DATTN_LDS>(
+        entry, "attn_wide_bwd_dq_kernel<dattn>", "attn_wide_bwd_dkv_kernel<dattn>", a, 1, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ from typing import Any, Dict
 
 import torch
 
-from .loss import TransformerTTSLoss
+from .loss import GuidedAttentionLoss, TransformerTTSLoss
 from .model import TransformerTTS
 from .utils.util import apply_teacher_forcing, get_noam_scheduler, get_teacher_forcing_ratio, prepare_batch
 
@@ -47,6 +47,13 @@ class LightningModule(_Base):
         self.example_batch = None
         self.log_interval = config['training'].get('log_interval', 100)
         self.sync_loss = config['training'].get('sync_loss_every_step', True)
+        # config['training']['guided_attention'] = {weight, sigma, heads?, layers?} (an extension): the grad forward returns
+        # differentiable alignments and `weight * guided` joins the total.  Absent or None: the step below is the reference's.
+        ga = config['training'].get('guided_attention')
+        self.guided = self.guided_weight = None
+        if ga is not None:
+            self.guided_weight = float(ga['weight'])
+            self.guided = GuidedAttentionLoss(sigma=ga.get('sigma', 0.4), heads=ga.get('heads'), layers=ga.get('layers'))
         # dropout / scheduled-sampling draws follow torch's process seed folded with the data-parallel rank (the reference
         # draws them from torch's global generator; replicas there differ because their generators advance differently).
         # Derived at the first training_step, not here: Lightning constructs the module before torch.distributed exists.
@@ -82,10 +89,17 @@ class LightningModule(_Base):
         # forward #2 (with grad) on the mixed input, loss against the ground truth.  The loss reads the three prediction tensors
         # only (lightning_module.py:78-79 of the reference discards the alignments of its output dict as well), so the per-head
         # attention maps are not written here either; `validation_step` / `forward()` return them as the reference does.
-        output = self.forward(phoneme, mel_mixed, phoneme_lens, melspec_lens,
-                              need_alignments=self.config['training'].get('train_step_alignments', False), memory=mem_grad,
-                              postnet_twin=post_twin)
+        if self.guided is not None:
+            output = self.forward(phoneme, mel_mixed, phoneme_lens, melspec_lens, need_alignments=True, alignments_grad=True,
+                                  memory=mem_grad, postnet_twin=post_twin)
+        else:
+            output = self.forward(phoneme, mel_mixed, phoneme_lens, melspec_lens,
+                                  need_alignments=self.config['training'].get('train_step_alignments', False), memory=mem_grad,
+                                  postnet_twin=post_twin)
         loss = self.criterion(output, melspec, melspec_lens)
+        if self.guided is not None:
+            loss['guided'] = self.guided(output['alignments'], phoneme_lens, melspec_lens)
+            loss['total'] = loss['total'] + self.guided_weight * loss['guided']
         if self.sync_loss:
             self.train_losses.append(loss['total'].item())
         else:

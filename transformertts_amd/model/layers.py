@@ -211,14 +211,20 @@ class MultiheadAttention(nn.Module):
         return self._out(ctx, residual, out_drop, skip, on_kernels)
 
     def cross_attention(self, x: Tensor, mem: Tensor, mem_lens: Tensor, residual: Tensor, out_drop: float,
-                        need_weights: bool = True, dead: Optional[Tensor] = None, add_mask: Optional[Tensor] = None, kv=None):
+                        need_weights: bool = True, dead: Optional[Tensor] = None, add_mask: Optional[Tensor] = None, kv=None,
+                        weights_grad: bool = False):
         """`kv`: None, or this layer's (k | v) HeadImage from the stack's one K/V projection of the memory
-        (`ops.cross_kv_projection`, TransformerDecoder.forward): the layer then projects only its queries"""
+        (`ops.cross_kv_projection`, TransformerDecoder.forward): the layer then projects only its queries.
+        `weights_grad` (with `need_weights`): the returned weights are differentiable; q and k | v are then projected in fp32
+        (no head image) and the attention runs on the 128-column kernels (`ops.cross_attention(..., weights_grad=True)`)"""
         d = self.embed_dim
         skip = ops.SkipToken() if residual is x else None
         masked = dead is not None or add_mask is not None
-        if kv is not None and masked:
-            raise ValueError("cross_attention: a pre-projected K/V image takes length masks only")
+        weights_grad = bool(weights_grad and need_weights)
+        if kv is not None and (masked or weights_grad):
+            raise ValueError("cross_attention: a pre-projected K/V image takes length masks only and gives no gradient of the weights")
+        if weights_grad:
+            masked = True        # (for the routing below: fp32 projections, no head image)
         wq, wkv = ops.param_rows(self.in_proj_weight, 0, d), ops.param_rows(self.in_proj_weight, d, 3 * d)
         img = kv is not None or (not masked and ops.head_image_ok(x, wq, self.num_heads, 1) and
                                  ops.head_image_ok(mem, wkv, self.num_heads, 2))
@@ -230,7 +236,10 @@ class MultiheadAttention(nn.Module):
         p = self._p()
         on_kernels = not masked or ops.attention_on_kernels(d, self.num_heads, add_mask)
         seed = ops.seeds.next() if p > 0 and on_kernels else 0
-        if masked:
+        if weights_grad:
+            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, True, dead=dead, add_mask=add_mask,
+                                            weights_grad=True)
+        elif masked:
             ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights, dead=dead, add_mask=add_mask)
         else:
             ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights)
@@ -327,7 +336,8 @@ class TransformerDecoderLayer(nn.Module):
                 memory_mask: Optional[Tensor] = None, tgt_key_padding_mask: Optional[Tensor] = None,
                 memory_key_padding_mask: Optional[Tensor] = None, tgt_is_causal: bool = True,
                 memory_is_causal: bool = False, tgt_lens: Optional[Tensor] = None,
-                memory_lens: Optional[Tensor] = None, need_alignments: bool = True, memory_kv=None):
+                memory_lens: Optional[Tensor] = None, need_alignments: bool = True, memory_kv=None,
+                alignments_grad: bool = False):
         if memory_is_causal and memory_mask is None:
             raise ValueError("TransformerDecoderLayer: memory_is_causal is a hint about memory_mask and needs one (as torch)")
         B, Tq, Tk, H = tgt.size(0), tgt.size(1), memory.size(1), self.self_attn.num_heads
@@ -346,6 +356,8 @@ class TransformerDecoderLayer(nn.Module):
         tr = self.training
         sa = dict(dead=tgt_dead, add_mask=tgt_add)
         ca = dict(dead=mem_dead, add_mask=mem_add)
+        if alignments_grad:
+            ca["weights_grad"] = True
         if self.norm_first:      # reference model/layers.py:41-45
             x1 = ops.layer_norm(tgt, self.norm1.weight, self.norm1.bias, self.norm1.eps)
             s = self.self_attn.self_attention(x1, tgt_lens, causal, residual=tgt, out_drop=self.dropout1.p if tr else 0.0, **sa)
@@ -381,8 +393,10 @@ class TransformerDecoder(nn.Module):
                 memory_mask: Optional[Tensor] = None, tgt_key_padding_mask: Optional[Tensor] = None,
                 memory_key_padding_mask: Optional[Tensor] = None, tgt_is_causal: Optional[bool] = None,
                 memory_is_causal: Optional[bool] = None, tgt_lens: Optional[Tensor] = None,
-                memory_lens: Optional[Tensor] = None, need_alignments: bool = True):
+                memory_lens: Optional[Tensor] = None, need_alignments: bool = True, alignments_grad: bool = False):
         B = tgt.size(0)
+        if alignments_grad and not need_alignments:
+            raise ValueError("TransformerDecoder: alignments_grad=True needs need_alignments=True")
         # prefix key-padding masks become lengths once, here; masks with holes travel on to the layers as tensors
         if tgt_key_padding_mask is not None:
             lens, dead = _lens_and_kpm(tgt_lens, tgt_key_padding_mask, B, tgt.size(1), tgt.device, "TransformerDecoder (tgt)")
@@ -400,7 +414,8 @@ class TransformerDecoder(nn.Module):
         # backward also sums the layers' memory gradients; otherwise one handle per layer, their gradients meeting in one launch
         attns = [layer.multihead_attn for layer in self.layers]
         H = attns[0].num_heads
-        fused = (memory_mask is None and memory_key_padding_mask is None and memory.dim() == 3 and
+        # (differentiable alignments: every layer projects its own K/V in fp32 -- no stack, no head image)
+        fused = (not alignments_grad and memory_mask is None and memory_key_padding_mask is None and memory.dim() == 3 and
                  ops.cross_kv_ok(memory, attns, H) and
                  ops.head_image_ok(tgt, attns[0].in_proj_weight.detach()[:memory.size(-1)], H, 1))
         if fused:
@@ -417,7 +432,8 @@ class TransformerDecoder(nn.Module):
                                    memory_key_padding_mask=memory_key_padding_mask,
                                    tgt_is_causal=True if tgt_is_causal is None else tgt_is_causal,
                                    memory_is_causal=bool(memory_is_causal), tgt_lens=tgt_lens,
-                                   memory_lens=memory_lens, need_alignments=need_alignments, memory_kv=kv)
+                                   memory_lens=memory_lens, need_alignments=need_alignments, memory_kv=kv,
+                                   **({"alignments_grad": True} if alignments_grad else {}))
             alignments.append(alignment)
         if self.norm is not None:
             tgt = ops.layer_norm(tgt, self.norm.weight, self.norm.bias, self.norm.eps)

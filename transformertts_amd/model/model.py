@@ -220,8 +220,13 @@ class TransformerTTS(nn.Module):
 
     def forward(self, phoneme: Tensor, melspec: Tensor, phoneme_lens: Tensor, melspec_lens: Tensor,
                 need_alignments: bool = True, need_stop: bool = True, memory: Tensor = None,
-                postnet_twin: "ops.PostnetTwin" = None) -> dict:
+                postnet_twin: "ops.PostnetTwin" = None, alignments_grad: bool = False) -> dict:
         """
+        `alignments_grad=True` (an extension, with `need_alignments=True`): the returned maps are differentiable, as the
+        reference's are (model/layers.py:68-74) -- a loss written on `output['alignments']`, such as
+        `transformertts_amd.loss.GuidedAttentionLoss`, then trains the model.  The cross-attention of every decoder layer takes
+        its fp32 route for that (own K/V projection, 128-column kernels).  Without the flag the maps are detached: a
+        loss on them changes the reported value and no gradient.
         `need_alignments=False` (an extension; the reference always returns them) skips writing the per-head
         cross-attention maps -- 267 MB per forward at batch 64 -- for callers that only want the mels, e.g. the
         no-grad first forward of `training_step`.  `alignments` is then a list of None.
@@ -245,6 +250,8 @@ class TransformerTTS(nn.Module):
             raise ValueError("TransformerTTS.forward: expected phoneme (B,Tp) and melspec (B,Tm,n_mels)")
         if phoneme_lens.device != phoneme.device or melspec_lens.device != melspec.device:
             raise ValueError("TransformerTTS.forward: lengths must live on the same device as the batch")
+        if alignments_grad and not need_alignments:
+            raise ValueError("TransformerTTS.forward: alignments_grad=True needs need_alignments=True")
         phoneme_lens = phoneme_lens.to(torch.int64)
         melspec_lens = melspec_lens.to(torch.int64)
         if memory is None:
@@ -254,7 +261,8 @@ class TransformerTTS(nn.Module):
         tgt = self.pe(self.dec_prenet(melspec, shift_right=True))
         tgt_out, alignments = self.decoder(tgt, memory, tgt_is_causal=True, memory_is_causal=False,
                                            tgt_lens=melspec_lens, memory_lens=phoneme_lens,
-                                           need_alignments=need_alignments)
+                                           need_alignments=need_alignments,
+                                           **({"alignments_grad": True} if alignments_grad else {}))
         first_of_pair = postnet_twin is not None and postnet_twin.full is None
         pred_melspec, pred_stop = ops.heads(tgt_out, self.linear1.linear.weight, self.linear1.linear.bias,
                                             self.linear2.linear.weight, self.linear2.linear.bias,

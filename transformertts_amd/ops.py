@@ -1917,6 +1917,43 @@ def _mask_args(dead: Optional[torch.Tensor], mask4: Optional[torch.Tensor], Tk: 
     return (*mk, _p(dead), 0 if dead is None else dead.stride(0))
 
 
+def _attn_wide_dattn_bwd(*args) -> None:
+    """`_attn_wide_masked_bwd` (the masks may both be absent) when the weights carry a gradient; `args` = every C-ABI argument up to
+    dattn_stride_h."""
+    _lib.check(_lib.load().ttts_attention_bwd_wide_dattn(*args, _stream()), "ttts_attention_bwd_wide_dattn")
+
+
+def _dattn_in_place(g: torch.Tensor, Tk: int) -> bool:
+    """can the kernels address this (B, H, Tq, Tk) gradient of the weights where it lies: fp32, unit column stride, rows a multiple
+    of 4 floats apart and >= Tk, batch / head strides >= 0 (0 = expanded) and multiples of 4, every slice 16-byte aligned, and the
+    Tq whole rows of every slice inside the storage.  Reads strides only (works on a CPU tensor)."""
+    if g.dtype != torch.float32 or g.dim() != 4 or g.shape[3] != Tk:
+        return False
+    B, H, Tq, _ = g.shape
+    sb, sh, sr, sc = g.stride()
+    sb, sh = (0 if B == 1 else sb), (0 if H == 1 else sh)
+    if not ((sc == 1 or Tk == 1) and (Tq == 1 or (sr % 4 == 0 and sr >= Tk)) and sb >= 0 and sh >= 0 and sb % 4 == 0 and sh % 4 == 0
+            and g.data_ptr() % 16 == 0):
+        return False
+    ld = sr if Tq > 1 else mask_row_stride(Tk)
+    end = g.storage_offset() + sb * (B - 1) + sh * (H - 1) + Tq * ld
+    return end * 4 <= g.untyped_storage().nbytes()
+
+
+def _dattn_operand(g: torch.Tensor, Tk: int) -> torch.Tensor:
+    """the incoming gradient of the weights as the kernels address it: in place when `_dattn_in_place`, else copied once into
+    zero-padded rows (as `_mask_operand` treats a mask)"""
+    if g.dtype != torch.float32:
+        g = g.to(torch.float32)
+    return g if _dattn_in_place(g, Tk) else pad_mask_rows(g)
+
+
+def _dattn_args(g4: torch.Tensor, Tk: int):
+    """(d_attn, ld_dattn, dattn_stride_b, dattn_stride_h) of ttts_attention_bwd_wide_dattn; g4: `_dattn_operand`'s"""
+    ld = g4.stride(2) if g4.shape[2] > 1 else mask_row_stride(Tk)
+    return _p(g4), ld, g4.stride(0) if g4.shape[0] > 1 else 0, g4.stride(1) if g4.shape[1] > 1 else 0
+
+
 def _off(t: torch.Tensor, col: int):
     return c_void_p(t.data_ptr() + 4 * col)
 
@@ -2189,11 +2226,16 @@ class AttentionFn(torch.autograd.Function):
     (Tq, Tk), with one exception: an `add_mask` the kernels cannot address in place (bool, another dtype, a row stride that is no
     multiple of 4 floats, a misaligned slice) is copied by `_mask_operand` and the COPY is saved -- for a per-(batch, head) mask
     that is one score matrix.  `pad_mask_rows` makes a mask that is used in place (the layers pass such a one).  No host read,
-    nothing from torch's generator: the call captures into a HIP graph."""
+    nothing from torch's generator: the call captures into a HIP graph.
+    `weights_grad` (with `need_weights`, non-causal): the returned weights are differentiable -- a loss written on them reaches q
+    and kv, as it does through nn.MultiheadAttention.  The call then runs on the 128-column kernels whatever the head width, the
+    written weights ARE saved (the one (B,H,Tq,Tk) tensor this Function keeps), and a backward that receives a gradient of the
+    weights goes to `ttts_attention_bwd_wide_dattn`; one that receives none runs today's entry points.  Without the flag the
+    weights stay detached."""
 
     @staticmethod
     def forward(ctx, q, kv, lens, n_head, causal, drop_p, seed, need_weights, q_amax=None, kv_amax=None, o_amax=None,
-                dead=None, add_mask=None):
+                dead=None, add_mask=None, weights_grad=False):
         q = _chk(q, "attention.q")
         kv = _chk(kv, "attention.kv") if kv is not None else None
         lens = _chk(lens, "attention.lens", torch.int64)
@@ -2203,6 +2245,9 @@ class AttentionFn(torch.autograd.Function):
         if hd > 128:
             raise ValueError(f"attention kernels take head_dim <= 128 (d_model {d}, heads {n_head}: head_dim {hd})")
         masked = dead is not None or add_mask is not None
+        weights_grad = bool(weights_grad and need_weights)
+        if weights_grad and causal:
+            raise ValueError("attention: the weights are written (and differentiated) by the non-causal form only")
         mask4 = None
         if masked:
             if dead is not None:
@@ -2215,7 +2260,7 @@ class AttentionFn(torch.autograd.Function):
                 if add_mask.requires_grad:
                     raise ValueError("attention: the kernels give no gradient of a mask (ops.masked_attention does)")
                 mask4 = _mask_operand(add_mask, B, n_head, Tq, Tk)
-        W = 128 if masked or hd > 64 else 64      # columns per head as the kernels see them
+        W = 128 if masked or hd > 64 or weights_grad else 64      # columns per head as the kernels see them
         if W == 128:
             q_amax = kv_amax = None      # exact fp32 products: no pre-scales
         else:
@@ -2243,24 +2288,27 @@ class AttentionFn(torch.autograd.Function):
         else:
             o = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
             _unpad_heads(o64, o, 0, d, B * Tq, n_head, hd, W)
-        ctx.save_for_backward(q, kv, o64, stat, lens, dead, mask4, *pads)
+        ctx.save_for_backward(q, kv, o64, stat, lens, dead, mask4, attn if weights_grad else None, *pads)
         ctx.amax = (q_amax, kv_amax)
         ctx.cfg = (n_head, causal, float(drop_p), seed, hd, W)
         ctx.ss = _ss()
         if attn is None:       # weights not requested: single-pass online softmax, nothing written
             attn = torch.empty(0, dtype=torch.float32, device=q.device)
-        ctx.mark_non_differentiable(attn)
+        if not weights_grad:
+            ctx.mark_non_differentiable(attn)
         ctx.set_materialize_grads(False)     # or the engine fills a zero "gradient" the size of the weights every backward
         return o, attn
 
     @staticmethod
-    def backward(ctx, do, _dattn):
-        if do is None:
-            return (None,) * 13
+    def backward(ctx, do, dattn):
+        if do is None and dattn is None:
+            return (None,) * 14
         lib = _lib.load()
-        q, kv, o64, stat, lens, dead, mask4, *pads = ctx.saved_tensors
+        q, kv, o64, stat, lens, dead, mask4, attn, *pads = ctx.saved_tensors
         n_head, causal, drop_p, seed, hd, W = ctx.cfg
         masked = dead is not None or mask4 is not None
+        if do is None:       # a loss on the weights alone: the context carries no gradient
+            do = torch.zeros(q.shape[0], q.shape[1], n_head * hd, dtype=torch.float32, device=q.device)
         do = _chk(do, "attention.do")
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv) if kv is not None else None
@@ -2279,7 +2327,10 @@ class AttentionFn(torch.autograd.Function):
         if W == 128:
             args = (*ins, _p(o64), _p(do64), _p(stat), _p(delta), *outs, _p(lens), B, n_head, Tq, Tk, *lds, n_head * W, *ldg,
                     1 if causal else 0, hd ** -0.5, drop_p, seed, ctx.ss)
-            if masked:
+            if dattn is not None:
+                g4 = _dattn_operand(dattn, Tk)
+                _attn_wide_dattn_bwd(*args, *_mask_args(dead, mask4, Tk), _p(attn), *_dattn_args(g4, Tk))
+            elif masked:
                 _attn_wide_masked_bwd(*args, *_mask_args(dead, mask4, Tk))
             else:
                 _attn_wide_bwd(*args)
@@ -2298,7 +2349,7 @@ class AttentionFn(torch.autograd.Function):
         if hd != W:
             for g, (t, c, ld) in zip(grads, gwins):
                 _unpad_heads(g, t, c, ld, g.shape[0], n_head, hd, W)
-        return dq, dkv, None, None, None, None, None, None, None, None, None, None, None
+        return dq, dkv, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _mask_needs_autograd(add_mask) -> bool:
@@ -2359,11 +2410,21 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
     return o
 
 
-def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_weights: bool = True, dead=None, add_mask=None):
+def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_weights: bool = True, dead=None, add_mask=None,
+                    weights_grad: bool = False):
     """q (B,Tq,d), kv (B,Tk,2d): both fp32 tensors, or both HeadImages (kv may be one layer's window of `cross_kv_projection`).
-    `dead` / `add_mask`: as in `self_attention`."""
+    `dead` / `add_mask`: as in `self_attention`.
+    `weights_grad` (with `need_weights`): the returned weights are differentiable (see AttentionFn): fp32 operands on the
+    128-column kernels at any head_dim <= 128; wider heads go to `masked_attention`, which autograd differentiates anyway.
+    Without it the weights are detached, as they always were."""
     d = q.shape[-1]
     hd = _head_width(d, n_head)
+    if weights_grad and need_weights:
+        if isinstance(q, HeadImage) or isinstance(kv, HeadImage) or _twin(q) is not None:
+            raise ValueError("cross_attention: differentiable weights take fp32 operands (no head image, no twin batch)")
+        if hd > 128 or _mask_needs_autograd(add_mask):
+            return masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p, dead, _finite_mask(add_mask))
+        return AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, True, None, None, None, dead, add_mask, True)
     if dead is not None or add_mask is not None:
         if isinstance(q, HeadImage) or isinstance(kv, HeadImage) or _twin(q) is not None:
             raise ValueError("cross_attention: a head image / twin batch takes length masks only")
@@ -2391,6 +2452,50 @@ def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_wei
     if o_am is not None:
         o._ttts_amax = o_am
     return o, attn
+
+
+class GuidedAttentionFn(torch.autograd.Function):
+    """Guided attention loss (csrc/guided.hip) over a list of alignment maps (B,H,Tm,Tp): sum A o W / (n_selected sum_b T_b N_b)
+    with the soft diagonal prior W of `sigma`; `head_mask`: 0 = every head, else bit h = head h counts.  -> the scalar.  The
+    backward writes ONE (B, Tm, ld) tensor (with a head selection: (B, H, Tm, ld)) and hands every map the same expanded view of
+    it, which `AttentionFn.backward` reads in place.  No host read in either direction."""
+
+    @staticmethod
+    def forward(ctx, phoneme_lens, melspec_lens, sigma, head_mask, *maps):
+        lib = _lib.load()
+        plens = _chk(phoneme_lens, "guided_attention.phoneme_lens", torch.int64)
+        mlens = _chk(melspec_lens, "guided_attention.melspec_lens", torch.int64)
+        if not maps:
+            raise ValueError("guided_attention: no alignment map")
+        maps = [_chk(m, "guided_attention.alignments") for m in maps]
+        B, H, Tm, Tp = maps[0].shape
+        for m in maps:
+            if tuple(m.shape) != (B, H, Tm, Tp):
+                raise ValueError(f"guided_attention: maps differ in shape ({tuple(m.shape)} against {(B, H, Tm, Tp)})")
+        if plens.shape[0] != B or mlens.shape[0] != B:
+            raise ValueError(f"guided_attention: expected {B} lengths, got {plens.shape[0]} and {mlens.shape[0]}")
+        n_sel = len(maps) * (bin(head_mask).count("1") if head_mask else H)
+        partials = torch.empty(len(maps), B * H * Tm, dtype=torch.float32, device=plens.device)
+        loss = torch.empty((), dtype=torch.float32, device=plens.device)
+        for i, m in enumerate(maps):
+            _lib.check(lib.ttts_guided_attention_fwd(_p(m), _p(plens), _p(mlens), head_mask, float(sigma), B, H, Tm, Tp, _p(partials),
+                                                     i, len(maps), n_sel, _p(loss) if i == len(maps) - 1 else None, _stream()),
+                       "ttts_guided_attention_fwd")
+        ctx.save_for_backward(plens, mlens)
+        ctx.cfg = (float(sigma), head_mask, n_sel, len(maps), B, H, Tm, Tp)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        plens, mlens = ctx.saved_tensors
+        sigma, head_mask, n_sel, n_maps, B, H, Tm, Tp = ctx.cfg
+        g = _chk(g, "guided_attention.grad")
+        ld = mask_row_stride(Tp)
+        d = torch.empty((B, H, Tm, ld) if head_mask else (B, Tm, ld), dtype=torch.float32, device=plens.device)
+        _lib.check(_lib.load().ttts_guided_attention_bwd(_p(g), _p(plens), _p(mlens), head_mask, sigma, n_sel, B, H, Tm, Tp, ld, _p(d),
+                                                         _stream()), "ttts_guided_attention_bwd")
+        view = d[..., :Tp] if head_mask else d[:, None, :, :Tp].expand(B, H, Tm, Tp)
+        return (None, None, None, None) + (view,) * n_maps
 
 
 # ----------------------------------------------------------------------------------------------- small pieces
