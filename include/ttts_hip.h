@@ -499,6 +499,53 @@ int ttts_guided_attention_fwd(const float* attn, const int64_t* phoneme_lens, co
                               float* loss_out, void* stream);
 int ttts_guided_attention_bwd(const float* g_loss, const int64_t* phoneme_lens, const int64_t* melspec_lens, uint64_t head_mask,
                               float sigma, int n_selected, int B, int H, int Tm, int Tp, int ld, float* d_attn, void* stream);
+/* ---- phoneme durations from the alignment maps (ABI v20; alignment.hip): what a Transformer-TTS teacher hands a
+ * non-autoregressive student (FastSpeech: focus rate, most diagonal head, frames per phoneme; Glow-TTS: monotonic alignment
+ * search).  In torch, over output['alignments'] (the per-head weights of model/layers.py:68-74, one (B,H,Tm,Tp) map per decoder
+ * layer): `attn.max(-1)`, `.argmax(-1)`, a host read to pick the head, `torch.bincount` per utterance -- three ATen passes over
+ * every map -- and a Python loop for the search.  Here: one pass over each map, one small kernel each for the choice, the
+ * counts and the search, every data-dependent decision on the device, nothing read back, no atomics on global memory, fixed
+ * summation orders (lane order, then the xor tree): the calls capture into a HIP graph and repeat bit for bit.
+ * Element (b, h, t, n) of a map is attn[b * ld_batch + h * ld_head + t * ld_row + n] (strides in floats, unit column stride, no
+ * alignment asked); T_b = melspec_lens[b] clamped to [0, Tm], N_b = phoneme_lens[b] clamped to [0, Tp] (int64, device).  Nothing at
+ * t >= T_b or n >= N_b is ever loaded.
+ *   rowstats   for map `layer` of L: argmax[layer][b][h][t] = the FIRST n < N_b with A[t][n] = max_n A[t][n] (torch.argmax's tie
+ *              rule; 0 for t >= T_b or N_b = 0), argmax being (L,B,H,Tm) int32; rowmax is (B,H,Tm) floats of scratch that the next
+ *              call may reuse; focus[layer][b][h] = (1 / T_b) sum_{t < T_b} max_n A[t][n], 0 when T_b = 0 or N_b = 0, focus being
+ *              (L,B,H) floats.
+ *   select     choice[b] = layer * H + head (int64, (B,)); choice_pairs, if not NULL, (B,2) = (layer, head).  Modes:
+ *              UTTERANCE  per b the largest focus[layer][b][head], ties to the lowest layer * H + head;
+ *              BATCH      one pair for every b, the largest sum_b focus over the rows with T_b, N_b > 0 (summed in b order), same ties;
+ *              FIXED      the given (layer, head).
+ *   durations_argmax   durations[b][n] = #{t < T_b : argmax[choice[b]][b][t] = n}, int64 (B,Tp), exact zeros at n >= N_b; a row
+ *              sums to T_b when N_b > 0.  valid (may be NULL): valid[b] = T_b > 0 and N_b > 0.
+ *   mas        on plane choice[b] of utterance b, with s[t][n] = logf(fmaxf(A[t][n], 1e-30f)): Q[0][0] = s[0][0],
+ *              Q[t][n] = s[t][n] + max(Q[t-1][n], Q[t-1][n-1]) over the cells with n <= t and N_b-1-n <= T_b-1-t (those from which
+ *              the end is still reachable); the path runs from (0, 0) to (T_b-1, N_b-1) and on a tie STAYS on its phoneme
+ *              (Q[t-1][n] >= Q[t-1][n-1]).  durations[b][n] = frames the path spends on n: >= 1 for n < N_b, summing to T_b, zeros
+ *              from N_b on.  valid[b] = 0 (uint8) and an all-zero row when T_b < N_b or a length is 0 -- no monotonic path visits
+ *              every phoneme.  The chosen plane lives in the map choice[b] names, so `maps` is a HOST array of L device pointers
+ *              that travels to the kernel by value (no device pointer table); all L maps share the strides.  ws: the stay / advance
+ *              bits, one per cell, 8-byte aligned, ttts_alignment_mas_workspace_bytes(B, Tm, Tp) bytes (0 for a non-positive size).
+ * Refused before any launch, naming the value: null pointers (a NULL entry of `maps` included), non-positive sizes, ld_row < Tp,
+ * negative ld_head / ld_batch, L > 16, a layer outside [0, L), B*H*Tm >= 2^31, an unknown mode, a FIXED (layer, head) outside
+ * (L, H), L*H > 1024 (select), Tp > 4096 (durations_argmax), Tp > 1024 (mas), a workspace that is misaligned or too small. */
+#define TTTS_ALIGN_MAX_MAPS 16
+#define TTTS_ALIGN_SELECT_UTTERANCE 0
+#define TTTS_ALIGN_SELECT_BATCH 1
+#define TTTS_ALIGN_SELECT_FIXED 2
+int ttts_alignment_rowstats(const float* attn, int64_t ld_row, int64_t ld_head, int64_t ld_batch, const int64_t* phoneme_lens,
+                            const int64_t* melspec_lens, int B, int H, int Tm, int Tp, int layer, int L, int32_t* argmax,
+                            float* rowmax, float* focus, void* stream);
+int ttts_alignment_select(const float* focus, const int64_t* phoneme_lens, const int64_t* melspec_lens, int L, int B, int H, int mode,
+                          int layer, int head, int64_t* choice, int64_t* choice_pairs, void* stream);
+int ttts_alignment_durations_argmax(const int32_t* argmax, const int64_t* choice, const int64_t* phoneme_lens,
+                                    const int64_t* melspec_lens, int L, int B, int H, int Tm, int Tp, int64_t* durations, uint8_t* valid,
+                                    void* stream);
+size_t ttts_alignment_mas_workspace_bytes(int B, int Tm, int Tp);
+int ttts_alignment_mas(const float* const* maps, int L, int64_t ld_row, int64_t ld_head, int64_t ld_batch, const int64_t* choice,
+                       const int64_t* phoneme_lens, const int64_t* melspec_lens, int B, int H, int Tm, int Tp, void* ws,
+                       size_t ws_bytes, int64_t* durations, uint8_t* valid, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -92,6 +92,11 @@ SIGNATURES = {
                                           P, L, P, P, L, L, L, P]),
     "ttts_guided_attention_fwd": (I, [P, P, P, U, F, I, I, I, I, P, I, I, I, P, P]),
     "ttts_guided_attention_bwd": (I, [P, P, P, U, F, I, I, I, I, I, I, P, P]),
+    "ttts_alignment_rowstats": (I, [P, L, L, L, P, P, I, I, I, I, I, I, P, P, P, P]),
+    "ttts_alignment_select": (I, [P, P, P, I, I, I, I, I, I, P, P, P]),
+    "ttts_alignment_durations_argmax": (I, [P, P, P, P, I, I, I, I, I, P, P, P]),
+    "ttts_alignment_mas_workspace_bytes": (Z, [I, I, I]),
+    "ttts_alignment_mas": (I, [P, I, L, L, L, P, P, P, I, I, I, I, P, Z, P, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),
