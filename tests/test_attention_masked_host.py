@@ -209,3 +209,66 @@ def test_masks_have_no_cpu_path_either():
     half = ops.twin_pair(full)[0]
     with pytest.raises(ValueError, match="length masks only"):
         ops.self_attention(half, torch.tensor([4]), 1, False, 0.0, 0, dead=dead)
+
+
+# where ops.self_attention / ops.cross_attention send a call, written out from their ladders as they stood before one function
+# (ops._attn_route) made the decision; one row per (caller, operands, mask tensor, weights_grad and need_weights), one letter per
+# head width of _WIDTHS.  Routes: A tensor algebra, W the 128-column kernels, I the head-image kernels, H fp16x3 on 64 columns;
+# refusals: the letters of _REFUSALS.
+_WIDTHS = (32, 64, 96, 128, 160)
+_ROUTES = {"A": "algebra", "W": "wide", "I": "image", "H": "h3"}
+_REFUSALS = {"L": "{who}: a head image / twin batch takes length masks only",
+             "F": "{who}: differentiable weights take fp32 operands (no head image, no twin batch)",
+             "C": "{who}: head images hold 64-column heads",
+             "T": "{who}: a twin batch runs on head images only"}
+_ROUTE_TABLE = [
+    # caller             operands  mask     weights_grad  32 .. 160
+    ("self_attention",  "fp32",   "none",  False, "HHWWA"),
+    ("self_attention",  "fp32",   "plain", False, "WWWWA"),
+    ("self_attention",  "fp32",   "grad",  False, "AAAAA"),
+    ("self_attention",  "twin",   "none",  False, "TTTTA"),      # (heads wider than 128 leave before the twin is looked at)
+    ("self_attention",  "twin",   "plain", False, "LLLLL"),
+    ("self_attention",  "twin",   "grad",  False, "LLLLL"),
+    ("self_attention",  "image",  "none",  False, "IICCC"),
+    ("self_attention",  "image",  "plain", False, "LLLLL"),
+    ("self_attention",  "image",  "grad",  False, "LLLLL"),
+    ("cross_attention", "fp32",   "none",  False, "HHWWA"),
+    ("cross_attention", "fp32",   "plain", False, "WWWWA"),
+    ("cross_attention", "fp32",   "grad",  False, "AAAAA"),
+    ("cross_attention", "twin",   "none",  False, "HHWWA"),      # (the cross form never looked at the twin of an unmasked call)
+    ("cross_attention", "twin",   "plain", False, "LLLLL"),
+    ("cross_attention", "twin",   "grad",  False, "LLLLL"),
+    ("cross_attention", "image",  "none",  False, "IICCC"),
+    ("cross_attention", "image",  "plain", False, "LLLLL"),
+    ("cross_attention", "image",  "grad",  False, "LLLLL"),
+    ("cross_attention", "fp32",   "none",  True,  "WWWWA"),
+    ("cross_attention", "fp32",   "plain", True,  "WWWWA"),
+    ("cross_attention", "fp32",   "grad",  True,  "AAAAA"),
+    ("cross_attention", "twin",   "none",  True,  "FFFFF"),
+    ("cross_attention", "twin",   "plain", True,  "FFFFF"),
+    ("cross_attention", "twin",   "grad",  True,  "FFFFF"),
+    ("cross_attention", "image",  "none",  True,  "FFFFF"),
+    ("cross_attention", "image",  "plain", True,  "FFFFF"),
+    ("cross_attention", "image",  "grad",  True,  "FFFFF"),
+]
+
+
+def test_the_route_of_an_attention_call():
+    from transformertts_amd import ops
+    masks = {"none": None, "plain": torch.zeros(4, 4), "grad": torch.zeros(4, 4, requires_grad=True)}
+    assert len({row[:4] for row in _ROUTE_TABLE}) == len(_ROUTE_TABLE) == 27
+    for who, operands, mask, weights_grad, expected in _ROUTE_TABLE:
+        m = masks[mask]
+        for hd, letter in zip(_WIDTHS, expected, strict=True):
+            args = (who, hd, operands == "image", operands == "twin", m is not None, ops._mask_needs_autograd(m), weights_grad)
+            if letter in _ROUTES:
+                assert ops._attn_route(*args) == _ROUTES[letter], args
+            else:
+                with pytest.raises(ValueError, match=re.escape(_REFUSALS[letter].format(who=who))):
+                    ops._attn_route(*args)
+    # ... and what the layers ask before they draw a seed is the same decision
+    for hd in _WIDTHS:
+        for mask in masks.values():
+            assert ops.attention_on_kernels(2 * hd, 2, mask) == (hd <= 128 and not (mask is not None and mask.requires_grad))
+    with torch.no_grad():       # nothing to differentiate: the mask is a plain one
+        assert ops.attention_on_kernels(256, 2, masks["grad"])

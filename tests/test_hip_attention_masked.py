@@ -378,16 +378,16 @@ def test_masked_layers_match_torch_on_the_kernels(monkeypatch):
     attention on the kernels -- counted at the launchers -- and none in ops.masked_attention"""
     from transformertts_amd import ops
     calls = {"kernels": 0, "algebra": 0}
-    fwd, algebra = ops._attn_wide_masked_fwd, ops.masked_attention
+    fwd, algebra = ops._attn_wide_fwd, ops.masked_attention
 
-    def count_fwd(*a, **k):
-        calls["kernels"] += 1
-        return fwd(*a, **k)
+    def count_fwd(*a, mask=None):
+        calls["kernels"] += mask is not None          # the masked entry point: the one launcher takes both forms
+        return fwd(*a, mask=mask)
 
     def count_algebra(*a, **k):
         calls["algebra"] += 1
         return algebra(*a, **k)
-    monkeypatch.setattr(ops, "_attn_wide_masked_fwd", count_fwd)
+    monkeypatch.setattr(ops, "_attn_wide_fwd", count_fwd)
     monkeypatch.setattr(ops, "masked_attention", count_algebra)
     masks.test_decoder_layer_with_arbitrary_masks_matches_torch(False)
     assert calls == {"kernels": 2, "algebra": 0}, calls

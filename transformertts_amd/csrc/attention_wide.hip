@@ -504,62 +504,122 @@ using namespace ttts;
 
 constexpr int WIDE_DATTN_LDS = 4 * 16 * 64 * 4;      // the dA columns of the DATTN dK/dV kernel: 16 floats per lane, dynamic LDS
 
+// ---- host side: the five entry points are names for two bodies, wide_fwd and wide_bwd.  An entry passes its own name (every
+// refusal starts with it), empty operands for what its signature lacks, and its form: WIDE_PLAIN takes no mask operands (the
+// kernels of AttnArgs), WIDE_MASKED requires at least one mask (the MASKED kernels), WIDE_DATTN (backward only) requires attn and
+// d_attn and takes masks or none (the DATTN kernels: non-causal, MASKED).  Order of the checks: null pointers, attn_check,
+// attn_check_grad_strides (backward), wide_dattn_check (WIDE_DATTN), wide_mask_check (a mask given or required), causal with
+// weights (forward), 16-byte alignment of the operands.
+enum WideForm { WIDE_PLAIN, WIDE_MASKED, WIDE_DATTN };
+// a (B | 1, H | 1, Tq, Tk) fp32 operand whose rows the kernels read where they lie: the additive mask, the gradient of the weights
+struct WideSlices { const float* p; long ld, stride_b, stride_h; };
+struct WideMask { WideSlices add; const uint8_t* key_dead; long ldd; };      // the mask operands of the _masked / _dattn entry points
+struct WideDattn { const float* attn; WideSlices d; };                       // ttts_attention_bwd_wide_dattn: the weights, their gradient
+
+// refused before any launch, each refusal naming its value; `what` / `ptr` / `ld` / `stride`: the operand's names in the refusals
+static int wide_slices_check(const char* name, const char* what, const char* ptr, const char* ld, const char* stride, const WideSlices& s,
+                             int Tq, int Tk) {
+    TTTS_REQUIRE(s.ld >= Tk && s.ld % 4 == 0, "%s: the %s row stride must be a multiple of 4 floats and >= Tk (%s %ld, Tk %d)",
+                 name, what, ld, s.ld, Tk);
+    TTTS_REQUIRE(s.stride_b >= 0 && s.stride_h >= 0, "%s: %s strides must not be negative (%s_stride_b %ld, %s_stride_h %ld)",
+                 name, what, stride, s.stride_b, stride, s.stride_h);
+    TTTS_REQUIRE(((uintptr_t)s.p & 15) == 0 && s.stride_b % 4 == 0 && s.stride_h % 4 == 0,
+                 "%s: %s must be 16-byte aligned in every (batch, head) slice (address %p, %s_stride_b %ld, %s_stride_h %ld)",
+                 name, ptr, (const void*)s.p, stride, s.stride_b, stride, s.stride_h);
+    TTTS_REQUIRE((long)Tq * s.ld < (1L << 30), "%s: one %s slice exceeds 4 GiB (Tq %d, %s %ld)", name, what, Tq, ld, s.ld);
+    return TTTS_OK;
+}
+static int wide_mask_check(const char* name, const WideMask& m, int Tq, int Tk) {
+    TTTS_REQUIRE(m.add.p || m.key_dead, "%s: add_mask and key_dead are both NULL (use the unmasked entry point)", name);
+    if (m.add.p) {
+        int rc = wide_slices_check(name, "mask", "add_mask", "ldm", "mask", m.add, Tq, Tk);
+        if (rc) return rc;
+    }
+    TTTS_REQUIRE(!m.key_dead || m.ldd >= Tk, "%s: the dead-key row stride must be >= Tk (ldd %ld, Tk %d)", name, m.ldd, Tk);
+    return TTTS_OK;
+}
+static void wide_mask_fill(AttnMaskArgs& a, const WideMask& m) {
+    a.add_mask = m.add.p; a.key_dead = m.key_dead;
+    a.mask_stride_b = m.add.stride_b; a.mask_stride_h = m.add.stride_h;
+    a.ldm = m.add.p ? (int)m.add.ld : 4; a.ldd = (int)m.ldd;
+}
+static int wide_dattn_check(const char* name, const WideDattn& g, int causal, int Tq, int Tk) {
+    TTTS_REQUIRE(g.attn, "%s: attn is NULL (the forward's weights are required)", name);
+    TTTS_REQUIRE(g.d.p, "%s: d_attn is NULL (use ttts_attention_bwd_wide / _masked without a gradient of the weights)", name);
+    TTTS_REQUIRE(!causal, "%s: the weights are only written by the non-causal (cross) form (causal %d)", name, causal);
+    return wide_slices_check(name, "d_attn", "d_attn", "ld_dattn", "dattn", g.d, Tq, Tk);
+}
+
+// One AttnDattnArgs is filled whatever the form; each launcher gets the base its kernels take (AttnArgs, AttnMaskArgs), i.e. the
+// leading bytes of it.  Without a mask the descriptors are empty (s + 0.f == s), which is what WIDE_DATTN runs on then.
+static int wide_fwd(const char* entry, WideForm form, const float* q, const float* k, const float* v, float* o, float* rowstat,
+                    float* attn, const int64_t* key_lens, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int causal,
+                    float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, const WideMask& m, hipStream_t stream) {
+    TTTS_REQUIRE(q && k && v && o && rowstat && key_lens, "%s: null pointer", entry);
+    int rc = attn_check(entry, WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc && form == WIDE_MASKED) rc = wide_mask_check(entry, m, Tq, Tk);
+    if (rc) return rc;
+    TTTS_REQUIRE(!(causal && attn), "%s: the weights are only written by the non-causal (cross) form", entry);
+    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "%s: q/k/v must be 16-byte aligned", entry);
+    AttnDattnArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    wide_mask_fill(a, m);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.rowstat = rowstat; a.attn = attn;
+    if (form == WIDE_MASKED)
+        return attn_launch_fwd("attn_wide_fwd_kernel<masked>", attn_wide_fwd_kernel<true, false, true>, attn_wide_fwd_kernel<false, true, true>,
+                               attn_wide_fwd_kernel<false, false, true>, causal, attn != nullptr, static_cast<const AttnMaskArgs&>(a), stream);
+    return attn_launch_fwd("attn_wide_fwd_kernel", ATTN_FWD_FORMS(attn_wide_fwd_kernel), causal, attn != nullptr,
+                           static_cast<const AttnArgs&>(a), stream);
+}
+
+static int wide_bwd(const char* entry, WideForm form, const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                    const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens, int B, int H, int Tq,
+                    int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv, int causal, float q_scale, float drop_p,
+                    uint64_t seed, const uint64_t* step_seed, const WideMask& m, const WideDattn& g, hipStream_t stream) {
+    TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "%s: null pointer", entry);
+    int rc = attn_check(entry, WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
+    if (!rc) rc = attn_check_grad_strides(entry, WHD, H, lddq, lddk, lddv);
+    if (!rc && form == WIDE_DATTN) rc = wide_dattn_check(entry, g, causal, Tq, Tk);
+    if (!rc && (form == WIDE_MASKED || (form == WIDE_DATTN && (m.add.p || m.key_dead)))) rc = wide_mask_check(entry, m, Tq, Tk);
+    if (rc) return rc;
+    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
+                 "%s: q/k/v/o/d_o must be 16-byte aligned", entry);
+    AttnDattnArgs a = {};
+    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
+    wide_mask_fill(a, m);
+    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
+    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
+    a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+    if (form == WIDE_DATTN) {
+        a.attn_w = g.attn; a.d_attn = g.d.p; a.ld_dattn = (int)g.d.ld;
+        a.dattn_stride_b = g.d.stride_b; a.dattn_stride_h = g.d.stride_h;
+        const long rows = (long)B * H * Tq;
+        TTTS_REQUIRE(rows < (1L << 32), "%s: grid too large (B*H*Tq %ld)", entry, rows);
+        hipLaunchKernelGGL(attn_dattn_rowdot_kernel, dim3((unsigned)cdiv(rows, 4L)), dim3(256), 0, stream, g.attn, g.d.p, g.d.stride_b,
+                           g.d.stride_h, (int)g.d.ld, delta, H, Tq, Tk, rows);
+        TTTS_LAUNCH_CHECK("attn_dattn_rowdot_kernel");
+        return attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true, true>, 0, &attn_wide_bwd_dkv_kernel<false, true, true>, WIDE_DATTN_LDS>(
+            entry, "attn_wide_bwd_dq_kernel<dattn>", "attn_wide_bwd_dkv_kernel<dattn>", a, 1, stream);
+    }
+    if (form == WIDE_MASKED) {
+        const AttnMaskArgs& am = a;
+        const char* names[2] = {"attn_wide_bwd_dq_kernel<masked>", "attn_wide_bwd_dkv_kernel<masked>"};
+        return causal ? attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<true, true>, 0, &attn_wide_bwd_dkv_kernel<true, true>, 0>(
+                            entry, names[0], names[1], am, 1, stream)
+                      : attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true>, 0, &attn_wide_bwd_dkv_kernel<false, true>, 0>(
+                            entry, names[0], names[1], am, 1, stream);
+    }
+    return ATTN_LAUNCH_BWD(attn_wide_bwd_dq_kernel, 0, attn_wide_bwd_dkv_kernel, 0, causal, entry, "attn_wide_bwd_dq_kernel",
+                           "attn_wide_bwd_dkv_kernel", static_cast<const AttnArgs&>(a), 1, stream);
+}
+
 extern "C" {
 
 int ttts_attention_fwd_wide(const float* q, const float* k, const float* v, float* o, float* rowstat, float* attn,
                             const int64_t* key_lens, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo,
                             int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream) {
-    TTTS_REQUIRE(q && k && v && o && rowstat && key_lens, "attention_fwd_wide: null pointer");
-    int rc = attn_check("attention_fwd_wide", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
-    if (rc) return rc;
-    TTTS_REQUIRE(!(causal && attn), "attention_fwd_wide: the weights are only written by the non-causal (cross) form");
-    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "attention_fwd_wide: q/k/v must be 16-byte aligned");
-    AttnArgs a = {};
-    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
-    a.q = q; a.k = k; a.v = v; a.o = o; a.rowstat = rowstat; a.attn = attn;
-    return attn_launch_fwd("attn_wide_fwd_kernel", ATTN_FWD_FORMS(attn_wide_fwd_kernel), causal, attn != nullptr, a, (hipStream_t)stream);
-}
-
-int ttts_attention_bwd_wide(const float* q, const float* k, const float* v, const float* o, const float* d_o,
-                            const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
-                            int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
-                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream) {
-    TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "attention_bwd_wide: null pointer");
-    int rc = attn_check("attention_bwd_wide", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
-    if (!rc) rc = attn_check_grad_strides("attention_bwd_wide", WHD, H, lddq, lddk, lddv);
-    if (rc) return rc;
-    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
-                 "attention_bwd_wide: q/k/v/o/d_o must be 16-byte aligned");
-    AttnArgs a = {};
-    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
-    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
-    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
-    a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    return ATTN_LAUNCH_BWD(attn_wide_bwd_dq_kernel, 0, attn_wide_bwd_dkv_kernel, 0, causal, "attention_bwd_wide", "attn_wide_bwd_dq_kernel",
-                           "attn_wide_bwd_dkv_kernel", a, 1, (hipStream_t)stream);
-}
-
-// the mask operands of the _masked entry points: refused before any launch, each refusal naming its value
-static int wide_mask_check(const char* name, const float* add_mask, long ldm, long stride_b, long stride_h, const uint8_t* key_dead,
-                           long ldd, int Tq, int Tk) {
-    TTTS_REQUIRE(add_mask || key_dead, "%s: add_mask and key_dead are both NULL (use the unmasked entry point)", name);
-    if (add_mask) {
-        TTTS_REQUIRE(ldm >= Tk && ldm % 4 == 0, "%s: the mask row stride must be a multiple of 4 floats and >= Tk (ldm %ld, Tk %d)",
-                     name, ldm, Tk);
-        TTTS_REQUIRE(stride_b >= 0 && stride_h >= 0, "%s: mask strides must not be negative (mask_stride_b %ld, mask_stride_h %ld)",
-                     name, stride_b, stride_h);
-        TTTS_REQUIRE(((uintptr_t)add_mask & 15) == 0 && stride_b % 4 == 0 && stride_h % 4 == 0,
-                     "%s: add_mask must be 16-byte aligned in every (batch, head) slice (address %p, mask_stride_b %ld, mask_stride_h %ld)",
-                     name, (const void*)add_mask, stride_b, stride_h);
-        TTTS_REQUIRE((long)Tq * ldm < (1L << 30), "%s: one mask slice exceeds 4 GiB (Tq %d, ldm %ld)", name, Tq, ldm);
-    }
-    TTTS_REQUIRE(!key_dead || ldd >= Tk, "%s: the dead-key row stride must be >= Tk (ldd %ld, Tk %d)", name, ldd, Tk);
-    return TTTS_OK;
-}
-static void wide_mask_fill(AttnMaskArgs& a, const float* add_mask, long ldm, long stride_b, long stride_h, const uint8_t* key_dead, long ldd) {
-    a.add_mask = add_mask; a.key_dead = key_dead;
-    a.mask_stride_b = stride_b; a.mask_stride_h = stride_h;
-    a.ldm = add_mask ? (int)ldm : 4; a.ldd = (int)ldd;
+    return wide_fwd("attention_fwd_wide", WIDE_PLAIN, q, k, v, o, rowstat, attn, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal,
+                    q_scale, drop_p, seed, step_seed, WideMask{}, (hipStream_t)stream);
 }
 
 int ttts_attention_fwd_wide_masked(const float* q, const float* k, const float* v, float* o, float* rowstat, float* attn,
@@ -567,18 +627,17 @@ int ttts_attention_fwd_wide_masked(const float* q, const float* k, const float* 
                                    int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
                                    const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
                                    const uint8_t* key_dead, int64_t ldd, void* stream) {
-    TTTS_REQUIRE(q && k && v && o && rowstat && key_lens, "attention_fwd_wide_masked: null pointer");
-    int rc = attn_check("attention_fwd_wide_masked", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
-    if (!rc) rc = wide_mask_check("attention_fwd_wide_masked", add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd, Tq, Tk);
-    if (rc) return rc;
-    TTTS_REQUIRE(!(causal && attn), "attention_fwd_wide_masked: the weights are only written by the non-causal (cross) form");
-    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "attention_fwd_wide_masked: q/k/v must be 16-byte aligned");
-    AttnMaskArgs a = {};
-    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
-    wide_mask_fill(a, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd);
-    a.q = q; a.k = k; a.v = v; a.o = o; a.rowstat = rowstat; a.attn = attn;
-    return attn_launch_fwd("attn_wide_fwd_kernel<masked>", attn_wide_fwd_kernel<true, false, true>, attn_wide_fwd_kernel<false, true, true>,
-                           attn_wide_fwd_kernel<false, false, true>, causal, attn != nullptr, a, (hipStream_t)stream);
+    return wide_fwd("attention_fwd_wide_masked", WIDE_MASKED, q, k, v, o, rowstat, attn, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo,
+                    causal, q_scale, drop_p, seed, step_seed, WideMask{{add_mask, ldm, mask_stride_b, mask_stride_h}, key_dead, ldd},
+                    (hipStream_t)stream);
+}
+
+int ttts_attention_bwd_wide(const float* q, const float* k, const float* v, const float* o, const float* d_o,
+                            const float* rowstat, float* delta, float* dq, float* dk, float* dv, const int64_t* key_lens,
+                            int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
+                            int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed, void* stream) {
+    return wide_bwd("attention_bwd_wide", WIDE_PLAIN, q, k, v, o, d_o, rowstat, delta, dq, dk, dv, key_lens, B, H, Tq, Tk, ldq, ldk, ldv,
+                    ldo, lddq, lddk, lddv, causal, q_scale, drop_p, seed, step_seed, WideMask{}, WideDattn{}, (hipStream_t)stream);
 }
 
 int ttts_attention_bwd_wide_masked(const float* q, const float* k, const float* v, const float* o, const float* d_o,
@@ -587,41 +646,9 @@ int ttts_attention_bwd_wide_masked(const float* q, const float* k, const float* 
                                    int causal, float q_scale, float drop_p, uint64_t seed, const uint64_t* step_seed,
                                    const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
                                    const uint8_t* key_dead, int64_t ldd, void* stream) {
-    TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "attention_bwd_wide_masked: null pointer");
-    int rc = attn_check("attention_bwd_wide_masked", WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
-    if (!rc) rc = attn_check_grad_strides("attention_bwd_wide_masked", WHD, H, lddq, lddk, lddv);
-    if (!rc) rc = wide_mask_check("attention_bwd_wide_masked", add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd, Tq, Tk);
-    if (rc) return rc;
-    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
-                 "attention_bwd_wide_masked: q/k/v/o/d_o must be 16-byte aligned");
-    AttnMaskArgs a = {};
-    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
-    wide_mask_fill(a, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd);
-    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
-    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
-    a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    const char* names[3] = {"attention_bwd_wide_masked", "attn_wide_bwd_dq_kernel<masked>", "attn_wide_bwd_dkv_kernel<masked>"};
-    return causal ? attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<true, true>, 0, &attn_wide_bwd_dkv_kernel<true, true>, 0>(
-                        names[0], names[1], names[2], a, 1, (hipStream_t)stream)
-                  : attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true>, 0, &attn_wide_bwd_dkv_kernel<false, true>, 0>(
-                        names[0], names[1], names[2], a, 1, (hipStream_t)stream);
-}
-
-// the gradient of the weights of ttts_attention_bwd_wide_dattn: refused before any launch, each refusal naming its value
-static int wide_dattn_check(const char* name, const float* attn, const float* d_attn, long ld, long stride_b, long stride_h, int causal,
-                            int Tq, int Tk) {
-    TTTS_REQUIRE(attn, "%s: attn is NULL (the forward's weights are required)", name);
-    TTTS_REQUIRE(d_attn, "%s: d_attn is NULL (use ttts_attention_bwd_wide / _masked without a gradient of the weights)", name);
-    TTTS_REQUIRE(!causal, "%s: the weights are only written by the non-causal (cross) form (causal %d)", name, causal);
-    TTTS_REQUIRE(ld >= Tk && ld % 4 == 0, "%s: the d_attn row stride must be a multiple of 4 floats and >= Tk (ld_dattn %ld, Tk %d)",
-                 name, ld, Tk);
-    TTTS_REQUIRE(stride_b >= 0 && stride_h >= 0, "%s: d_attn strides must not be negative (dattn_stride_b %ld, dattn_stride_h %ld)",
-                 name, stride_b, stride_h);
-    TTTS_REQUIRE(((uintptr_t)d_attn & 15) == 0 && stride_b % 4 == 0 && stride_h % 4 == 0,
-                 "%s: d_attn must be 16-byte aligned in every (batch, head) slice (address %p, dattn_stride_b %ld, dattn_stride_h %ld)",
-                 name, (const void*)d_attn, stride_b, stride_h);
-    TTTS_REQUIRE((long)Tq * ld < (1L << 30), "%s: one d_attn slice exceeds 4 GiB (Tq %d, ld_dattn %ld)", name, Tq, ld);
-    return TTTS_OK;
+    return wide_bwd("attention_bwd_wide_masked", WIDE_MASKED, q, k, v, o, d_o, rowstat, delta, dq, dk, dv, key_lens, B, H, Tq, Tk, ldq,
+                    ldk, ldv, ldo, lddq, lddk, lddv, causal, q_scale, drop_p, seed, step_seed,
+                    WideMask{{add_mask, ldm, mask_stride_b, mask_stride_h}, key_dead, ldd}, WideDattn{}, (hipStream_t)stream);
 }
 
 int ttts_attention_bwd_wide_dattn(const float* q, const float* k, const float* v, const float* o, const float* d_o,
@@ -631,30 +658,10 @@ int ttts_attention_bwd_wide_dattn(const float* q, const float* k, const float* v
                                   const float* add_mask, int64_t ldm, int64_t mask_stride_b, int64_t mask_stride_h,
                                   const uint8_t* key_dead, int64_t ldd, const float* attn, const float* d_attn, int64_t ld_dattn,
                                   int64_t dattn_stride_b, int64_t dattn_stride_h, void* stream) {
-    const char* entry = "attention_bwd_wide_dattn";
-    TTTS_REQUIRE(q && k && v && o && d_o && rowstat && delta && dq && dk && dv && key_lens, "%s: null pointer", entry);
-    int rc = attn_check(entry, WHD, B, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, drop_p);
-    if (!rc) rc = attn_check_grad_strides(entry, WHD, H, lddq, lddk, lddv);
-    if (!rc) rc = wide_dattn_check(entry, attn, d_attn, ld_dattn, dattn_stride_b, dattn_stride_h, causal, Tq, Tk);
-    if (!rc && (add_mask || key_dead)) rc = wide_mask_check(entry, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd, Tq, Tk);
-    if (rc) return rc;
-    TTTS_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) & 15) == 0,
-                 "%s: q/k/v/o/d_o must be 16-byte aligned", entry);
-    AttnDattnArgs a = {};
-    attn_fill(a, key_lens, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_scale, drop_p, seed, step_seed);
-    wide_mask_fill(a, add_mask, ldm, mask_stride_b, mask_stride_h, key_dead, ldd);      // both NULL: empty descriptors, s + 0.f == s
-    a.q = q; a.k = k; a.v = v; a.o = const_cast<float*>(o); a.dout = d_o; a.rowstat = const_cast<float*>(rowstat);
-    a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv;
-    a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.attn_w = attn; a.d_attn = d_attn; a.ld_dattn = (int)ld_dattn;
-    a.dattn_stride_b = dattn_stride_b; a.dattn_stride_h = dattn_stride_h;
-    const long rows = (long)B * H * Tq;
-    TTTS_REQUIRE(rows < (1L << 32), "%s: grid too large (B*H*Tq %ld)", entry, rows);
-    hipLaunchKernelGGL(attn_dattn_rowdot_kernel, dim3((unsigned)cdiv(rows, 4L)), dim3(256), 0, (hipStream_t)stream, attn, d_attn,
-                       (long)dattn_stride_b, (long)dattn_stride_h, (int)ld_dattn, delta, H, Tq, Tk, rows);
-    TTTS_LAUNCH_CHECK("attn_dattn_rowdot_kernel");
-    return attn_launch_bwd_pair<&attn_wide_bwd_dq_kernel<false, true, true>, 0, &attn_wide_bwd_dkv_kernel<false, true, true>, WIDE_DATTN_LDS>(
-        entry, "attn_wide_bwd_dq_kernel<dattn>", "attn_wide_bwd_dkv_kernel<dattn>", a, 1, (hipStream_t)stream);
+    return wide_bwd("attention_bwd_wide_dattn", WIDE_DATTN, q, k, v, o, d_o, rowstat, delta, dq, dk, dv, key_lens, B, H, Tq, Tk, ldq,
+                    ldk, ldv, ldo, lddq, lddk, lddv, causal, q_scale, drop_p, seed, step_seed,
+                    WideMask{{add_mask, ldm, mask_stride_b, mask_stride_h}, key_dead, ldd},
+                    WideDattn{attn, {d_attn, ld_dattn, dattn_stride_b, dattn_stride_h}}, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -204,10 +204,7 @@ class MultiheadAttention(nn.Module):
         p = self._p()
         on_kernels = not masked or ops.attention_on_kernels(self.embed_dim, self.num_heads, add_mask)
         seed = ops.seeds.next() if p > 0 and on_kernels else 0       # (the tensor-algebra route draws from torch's generator)
-        if masked:
-            ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, seed, dead=dead, add_mask=add_mask)
-        else:
-            ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, seed)
+        ctx = ops.self_attention(qkv, lens, self.num_heads, causal, p, seed, dead=dead, add_mask=add_mask)
         return self._out(ctx, residual, out_drop, skip, on_kernels)
 
     def cross_attention(self, x: Tensor, mem: Tensor, mem_lens: Tensor, residual: Tensor, out_drop: float,
@@ -223,10 +220,9 @@ class MultiheadAttention(nn.Module):
         weights_grad = bool(weights_grad and need_weights)
         if kv is not None and (masked or weights_grad):
             raise ValueError("cross_attention: a pre-projected K/V image takes length masks only and gives no gradient of the weights")
-        if weights_grad:
-            masked = True        # (for the routing below: fp32 projections, no head image)
+        fp32_route = masked or weights_grad      # fp32 projections, no head image: what masks and differentiable weights run on
         wq, wkv = ops.param_rows(self.in_proj_weight, 0, d), ops.param_rows(self.in_proj_weight, d, 3 * d)
-        img = kv is not None or (not masked and ops.head_image_ok(x, wq, self.num_heads, 1) and
+        img = kv is not None or (not fp32_route and ops.head_image_ok(x, wq, self.num_heads, 1) and
                                  ops.head_image_ok(mem, wkv, self.num_heads, 2))
         q = ops.linear(x, wq, ops.param_rows(self.in_proj_bias, 0, d), skip_in=skip, publish_amax=not img,
                        head_image_sections=1 if img else 0)
@@ -234,15 +230,10 @@ class MultiheadAttention(nn.Module):
             kv = ops.linear(mem, wkv, ops.param_rows(self.in_proj_bias, d, 3 * d), publish_amax=not img,
                             head_image_sections=2 if img else 0)
         p = self._p()
-        on_kernels = not masked or ops.attention_on_kernels(d, self.num_heads, add_mask)
+        on_kernels = not fp32_route or ops.attention_on_kernels(d, self.num_heads, add_mask)
         seed = ops.seeds.next() if p > 0 and on_kernels else 0
-        if weights_grad:
-            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, True, dead=dead, add_mask=add_mask,
-                                            weights_grad=True)
-        elif masked:
-            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights, dead=dead, add_mask=add_mask)
-        else:
-            ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights)
+        ctx, attn = ops.cross_attention(q, kv, mem_lens, self.num_heads, p, seed, need_weights, dead=dead, add_mask=add_mask,
+                                        weights_grad=weights_grad)
         return self._out(ctx, residual, out_drop, skip, on_kernels), (attn if need_weights else None)
 
 
@@ -355,9 +346,7 @@ class TransformerDecoderLayer(nn.Module):
         mem_add = None if memory_mask is None else _additive_mask(memory_mask, B, H, Tq, Tk)
         tr = self.training
         sa = dict(dead=tgt_dead, add_mask=tgt_add)
-        ca = dict(dead=mem_dead, add_mask=mem_add)
-        if alignments_grad:
-            ca["weights_grad"] = True
+        ca = dict(dead=mem_dead, add_mask=mem_add, weights_grad=alignments_grad)
         if self.norm_first:      # reference model/layers.py:41-45
             x1 = ops.layer_norm(tgt, self.norm1.weight, self.norm1.bias, self.norm1.eps)
             s = self.self_attn.self_attention(x1, tgt_lens, causal, residual=tgt, out_drop=self.dropout1.p if tr else 0.0, **sa)
@@ -433,7 +422,7 @@ class TransformerDecoder(nn.Module):
                                    tgt_is_causal=True if tgt_is_causal is None else tgt_is_causal,
                                    memory_is_causal=bool(memory_is_causal), tgt_lens=tgt_lens,
                                    memory_lens=memory_lens, need_alignments=need_alignments, memory_kv=kv,
-                                   **({"alignments_grad": True} if alignments_grad else {}))
+                                   alignments_grad=alignments_grad)
             alignments.append(alignment)
         if self.norm is not None:
             tgt = ops.layer_norm(tgt, self.norm.weight, self.norm.bias, self.norm.eps)

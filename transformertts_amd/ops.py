@@ -1820,39 +1820,32 @@ def _attn_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, 
     return o, stat, attn
 
 
-def _attn_wide_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_scale: float):
+def _attn_wide_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_scale: float, mask=None):
     """Heads of 128 columns on the fp32-MFMA kernels of csrc/attention_wide.hip (no operand maxima: exact fp32 products).
+    `mask`: None, or the six mask arguments of the C ABI (`_mask_args`): the call then goes to the masked entry point.
     -> (o (B, Tq, H * 128), stat, attn); stat (2, B, H, Tq) = the row maxima and row sums the backward re-forms the weights from."""
     dev = lens.device
     o = torch.empty(B, Tq, H * 128, dtype=torch.float32, device=dev)
     stat = torch.empty(2, B, H, Tq, dtype=torch.float32, device=dev)
     attn = torch.empty(B, H, Tq, Tk, dtype=torch.float32, device=dev) if need_weights else None
-    _lib.check(_lib.load().ttts_attention_fwd_wide(q, k, v, _p(o), _p(stat), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv,
-                                                   H * 128, 1 if causal else 0, float(q_scale), float(drop_p), seed, _ss(),
-                                                   _stream()), "ttts_attention_fwd_wide")
+    name = "ttts_attention_fwd_wide" if mask is None else "ttts_attention_fwd_wide_masked"
+    _lib.check(getattr(_lib.load(), name)(q, k, v, _p(o), _p(stat), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv, H * 128,
+                                          1 if causal else 0, float(q_scale), float(drop_p), seed, _ss(), *(mask or ()), _stream()),
+               name)
     return o, stat, attn
 
 
-def _attn_wide_bwd(*args) -> None:
-    """Backward of `_attn_wide_fwd`; `args` = every C-ABI argument up to step_seed."""
-    _lib.check(_lib.load().ttts_attention_bwd_wide(*args, _stream()), "ttts_attention_bwd_wide")
-
-
-def _attn_wide_masked_fwd(q, k, v, ldq, ldk, ldv, B, H, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_scale: float, mask):
-    """`_attn_wide_fwd` under tensor masks; `mask`: the six mask arguments of the C ABI (`_mask_args`)."""
-    dev = lens.device
-    o = torch.empty(B, Tq, H * 128, dtype=torch.float32, device=dev)
-    stat = torch.empty(2, B, H, Tq, dtype=torch.float32, device=dev)
-    attn = torch.empty(B, H, Tq, Tk, dtype=torch.float32, device=dev) if need_weights else None
-    _lib.check(_lib.load().ttts_attention_fwd_wide_masked(q, k, v, _p(o), _p(stat), _p(attn), _p(lens), B, H, Tq, Tk, ldq, ldk, ldv,
-                                                          H * 128, 1 if causal else 0, float(q_scale), float(drop_p), seed,
-                                                          _ss(), *mask, _stream()), "ttts_attention_fwd_wide_masked")
-    return o, stat, attn
-
-
-def _attn_wide_masked_bwd(*args) -> None:
-    """Backward of `_attn_wide_masked_fwd`; `args` = every C-ABI argument up to ldd."""
-    _lib.check(_lib.load().ttts_attention_bwd_wide_masked(*args, _stream()), "ttts_attention_bwd_wide_masked")
+def _attn_wide_bwd(args, mask=None, dattn=None) -> None:
+    """Backward of `_attn_wide_fwd`; `args`: every C-ABI argument up to step_seed; `mask`: None or `_mask_args`; `dattn`: None, or
+    (attn pointer, *`_dattn_args`) when the weights carry a gradient (the masks may then both be absent).  The entry point
+    follows from which of the two are given."""
+    if dattn is not None:
+        name, tail = "ttts_attention_bwd_wide_dattn", (*(mask or _mask_args(None, None, 0)), *dattn)
+    elif mask is not None:
+        name, tail = "ttts_attention_bwd_wide_masked", mask
+    else:
+        name, tail = "ttts_attention_bwd_wide", ()
+    _lib.check(getattr(_lib.load(), name)(*args, *tail, _stream()), name)
 
 
 def mask_row_stride(Tk: int) -> int:
@@ -1889,20 +1882,30 @@ def _mask_operand(add_mask: torch.Tensor, B: int, H: int, Tq: int, Tk: int) -> t
         m = _finite_mask(m)
     elif m.dtype != torch.float32:
         m = m.to(torch.float32)
-    sb, sh, sr, sc = m.stride()
-    if m.shape[0] == 1:
-        sb = 0
-    if m.shape[1] == 1:
-        sh = 0
-    ok = (sc == 1 or Tk == 1) and (sr % 4 == 0 and sr >= Tk or Tq == 1) and sb % 4 == 0 and sh % 4 == 0 and sb >= 0 and sh >= 0 \
-        and m.data_ptr() % 16 == 0
-    if ok:      # the kernels address whole rows of every slice (Tq rows of `ldm` floats): they must lie inside the storage
-        ldm = sr if Tq > 1 else mask_row_stride(Tk)
-        end = m.storage_offset() + sb * (m.shape[0] - 1) + sh * (m.shape[1] - 1) + Tq * ldm
-        ok = end * 4 <= m.untyped_storage().nbytes()
-    if not ok:
-        m = pad_mask_rows(m)
-    return m
+    return m if _rows_in_place(m, Tk) else pad_mask_rows(m)
+
+
+def _rows_in_place(t: torch.Tensor, Tk: int) -> bool:
+    """can the kernels address the Tq rows of every (batch, head) slice of this (B, H, Tq, Tk) tensor where they lie: fp32, unit
+    column stride, rows a multiple of 4 floats apart and >= Tk, batch / head strides >= 0 (0 = expanded) and multiples of 4, every
+    slice 16-byte aligned, and the Tq whole rows of every slice inside the storage.  Reads strides only (works on a CPU tensor)."""
+    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] != Tk:
+        return False
+    B, H, Tq, _ = t.shape
+    sb, sh, sr, sc = t.stride()
+    sb, sh = (0 if B == 1 else sb), (0 if H == 1 else sh)
+    if not ((sc == 1 or Tk == 1) and (Tq == 1 or (sr % 4 == 0 and sr >= Tk)) and sb >= 0 and sh >= 0 and sb % 4 == 0 and sh % 4 == 0
+            and t.data_ptr() % 16 == 0):
+        return False
+    ld = sr if Tq > 1 else mask_row_stride(Tk)
+    end = t.storage_offset() + sb * (B - 1) + sh * (H - 1) + Tq * ld
+    return end * 4 <= t.untyped_storage().nbytes()
+
+
+def _rows_args(t4: torch.Tensor, Tk: int):
+    """(pointer, row stride, batch stride, head stride) of a tensor `_rows_in_place` accepts, as the C entry points take them"""
+    ld = t4.stride(2) if t4.shape[2] > 1 else mask_row_stride(Tk)
+    return _p(t4), ld, t4.stride(0) if t4.shape[0] > 1 else 0, t4.stride(1) if t4.shape[1] > 1 else 0
 
 
 def _mask_args(dead: Optional[torch.Tensor], mask4: Optional[torch.Tensor], Tk: int):
@@ -1910,34 +1913,15 @@ def _mask_args(dead: Optional[torch.Tensor], mask4: Optional[torch.Tensor], Tk: 
     if mask4 is None:
         mk = (None, 0, 0, 0)
     else:
-        ldm = mask4.stride(2) if mask4.shape[2] > 1 else mask_row_stride(Tk)
         if mask4.shape[2] == 1 and mask4.shape[3] > 1 and mask4.stride(3) != 1:
             raise ValueError("attention mask: columns must be contiguous")
-        mk = (_p(mask4), ldm, mask4.stride(0) if mask4.shape[0] > 1 else 0, mask4.stride(1) if mask4.shape[1] > 1 else 0)
+        mk = _rows_args(mask4, Tk)
     return (*mk, _p(dead), 0 if dead is None else dead.stride(0))
 
 
-def _attn_wide_dattn_bwd(*args) -> None:
-    """`_attn_wide_masked_bwd` (the masks may both be absent) when the weights carry a gradient; `args` = every C-ABI argument up to
-    dattn_stride_h."""
-    _lib.check(_lib.load().ttts_attention_bwd_wide_dattn(*args, _stream()), "ttts_attention_bwd_wide_dattn")
-
-
 def _dattn_in_place(g: torch.Tensor, Tk: int) -> bool:
-    """can the kernels address this (B, H, Tq, Tk) gradient of the weights where it lies: fp32, unit column stride, rows a multiple
-    of 4 floats apart and >= Tk, batch / head strides >= 0 (0 = expanded) and multiples of 4, every slice 16-byte aligned, and the
-    Tq whole rows of every slice inside the storage.  Reads strides only (works on a CPU tensor)."""
-    if g.dtype != torch.float32 or g.dim() != 4 or g.shape[3] != Tk:
-        return False
-    B, H, Tq, _ = g.shape
-    sb, sh, sr, sc = g.stride()
-    sb, sh = (0 if B == 1 else sb), (0 if H == 1 else sh)
-    if not ((sc == 1 or Tk == 1) and (Tq == 1 or (sr % 4 == 0 and sr >= Tk)) and sb >= 0 and sh >= 0 and sb % 4 == 0 and sh % 4 == 0
-            and g.data_ptr() % 16 == 0):
-        return False
-    ld = sr if Tq > 1 else mask_row_stride(Tk)
-    end = g.storage_offset() + sb * (B - 1) + sh * (H - 1) + Tq * ld
-    return end * 4 <= g.untyped_storage().nbytes()
+    """can the kernels address this (B, H, Tq, Tk) gradient of the weights where it lies (`_rows_in_place`)"""
+    return _rows_in_place(g, Tk)
 
 
 def _dattn_operand(g: torch.Tensor, Tk: int) -> torch.Tensor:
@@ -1950,8 +1934,7 @@ def _dattn_operand(g: torch.Tensor, Tk: int) -> torch.Tensor:
 
 def _dattn_args(g4: torch.Tensor, Tk: int):
     """(d_attn, ld_dattn, dattn_stride_b, dattn_stride_h) of ttts_attention_bwd_wide_dattn; g4: `_dattn_operand`'s"""
-    ld = g4.stride(2) if g4.shape[2] > 1 else mask_row_stride(Tk)
-    return _p(g4), ld, g4.stride(0) if g4.shape[0] > 1 else 0, g4.stride(1) if g4.shape[1] > 1 else 0
+    return _rows_args(g4, Tk)
 
 
 def _off(t: torch.Tensor, col: int):
@@ -2230,8 +2213,8 @@ class AttentionFn(torch.autograd.Function):
     `weights_grad` (with `need_weights`, non-causal): the returned weights are differentiable -- a loss written on them reaches q
     and kv, as it does through nn.MultiheadAttention.  The call then runs on the 128-column kernels whatever the head width, the
     written weights ARE saved (the one (B,H,Tq,Tk) tensor this Function keeps), and a backward that receives a gradient of the
-    weights goes to `ttts_attention_bwd_wide_dattn`; one that receives none runs today's entry points.  Without the flag the
-    weights stay detached."""
+    weights goes to `ttts_attention_bwd_wide_dattn`; one that receives none runs `ttts_attention_bwd_wide` / `_masked`, as without the
+    flag (`_attn_wide_bwd`).  Without the flag the weights stay detached."""
 
     @staticmethod
     def forward(ctx, q, kv, lens, n_head, causal, drop_p, seed, need_weights, q_amax=None, kv_amax=None, o_amax=None,
@@ -2274,11 +2257,9 @@ class AttentionFn(torch.autograd.Function):
         else:
             pads = tuple(_pad_heads(t, c, ld, B * t.shape[1], n_head, hd, W) for t, c, ld in wins)
             ptrs, lds = [_p(t) for t in pads], [n_head * W] * 3
-        if masked:
-            o64, stat, attn = _attn_wide_masked_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights,
-                                                    hd ** -0.5, _mask_args(dead, mask4, Tk))
-        elif W == 128:
-            o64, stat, attn = _attn_wide_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, hd ** -0.5)
+        if W == 128:
+            o64, stat, attn = _attn_wide_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, hd ** -0.5,
+                                             mask=_mask_args(dead, mask4, Tk) if masked else None)
         else:
             o64, stat, attn = _attn_fwd(*ptrs, *lds, B, n_head, Tq, Tk, lens, causal, drop_p, seed, need_weights, q_amax,
                                         kv_amax, kv_amax, o_amax, q_scale=hd ** -0.5)
@@ -2327,13 +2308,9 @@ class AttentionFn(torch.autograd.Function):
         if W == 128:
             args = (*ins, _p(o64), _p(do64), _p(stat), _p(delta), *outs, _p(lens), B, n_head, Tq, Tk, *lds, n_head * W, *ldg,
                     1 if causal else 0, hd ** -0.5, drop_p, seed, ctx.ss)
-            if dattn is not None:
-                g4 = _dattn_operand(dattn, Tk)
-                _attn_wide_dattn_bwd(*args, *_mask_args(dead, mask4, Tk), _p(attn), *_dattn_args(g4, Tk))
-            elif masked:
-                _attn_wide_masked_bwd(*args, *_mask_args(dead, mask4, Tk))
-            else:
-                _attn_wide_bwd(*args)
+            g4 = None if dattn is None else _dattn_operand(dattn, Tk)
+            _attn_wide_bwd(args, _mask_args(dead, mask4, Tk) if masked else None,
+                           None if g4 is None else (_p(attn), *_dattn_args(g4, Tk)))
         else:
             lse, rowstat = stat[0], stat[1:]
             # max|dq|, max|dk, dv| for the in-projection gradients: ONE array for the one gradient of a packed projection
@@ -2366,9 +2343,36 @@ def _finite_mask(add_mask):
     return add_mask.clamp_min(big)
 
 
+def _attn_route(who: str, hd: int, image: bool, twin: bool, mask: bool, mask_grad: bool, weights_grad: bool) -> str:
+    """The one decision of `self_attention` / `cross_attention` (`who`: the name its refusals start with): where a call runs.
+      hd            columns per head (`_head_width`)
+      image / twin  the operands are head images / fp32 and the first half of a twin batch
+      mask          a mask tensor (`dead` / `add_mask`) is present;  mask_grad: `_mask_needs_autograd` of it
+      weights_grad  the returned weights are to be differentiable (`weights_grad and need_weights`)
+    -> "algebra" (`masked_attention`), "wide" (the 128-column kernels), "image" (the head-image kernels) or "h3" (fp16x3 on 64
+    columns).  Precedence: weights_grad, masks, width, images.  No tensor work."""
+    if weights_grad or mask:
+        if image or twin:
+            raise ValueError(f"{who}: differentiable weights take fp32 operands (no head image, no twin batch)" if weights_grad else
+                             f"{who}: a head image / twin batch takes length masks only")
+        return "algebra" if hd > 128 or mask_grad else "wide"
+    if hd > 64 and image:
+        raise ValueError(f"{who}: head images hold 64-column heads")
+    if hd > 128:
+        return "algebra"
+    if image:
+        return "image"
+    # only self_attention is handed twin batches (the encoder's) and refuses one that is no head image; cross_attention, whose
+    # query is the decoder's, never looked at the twin of an unmasked call (DESIGN.md 16a)
+    if twin and who == "self_attention":
+        raise ValueError(f"{who}: a twin batch runs on head images only")
+    return "wide" if hd > 64 else "h3"
+
+
 def attention_on_kernels(d: int, n_head: int, add_mask=None) -> bool:
     """does `self_attention` / `cross_attention` run this configuration on the attention kernels (else: `masked_attention`)"""
-    return _head_width(d, n_head) <= 128 and not _mask_needs_autograd(add_mask)
+    return _attn_route("attention", _head_width(d, n_head), False, False, add_mask is not None, _mask_needs_autograd(add_mask),
+                       False) != "algebra"
 
 
 def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: int, dead=None, add_mask=None):
@@ -2378,33 +2382,22 @@ def self_attention(qkv, lens, n_head: int, causal: bool, drop_p: float, seed: in
     `dead` / `add_mask` (see AttentionFn): masks that are tensors; fp32 operands and head_dim <= 128 run on the masked 128-column
     kernels.  Wider heads and a float mask that requires grad go to `masked_attention` (torch's generator draws their dropout)."""
     d = qkv.shape[-1] // 3
-    hd = _head_width(d, n_head)
-    if dead is not None or add_mask is not None:
-        if isinstance(qkv, HeadImage) or _twin(qkv) is not None:
-            raise ValueError("self_attention: a head image / twin batch takes length masks only")
-        if hd > 128 or _mask_needs_autograd(add_mask):
-            return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p, dead,
-                                    _finite_mask(add_mask))[0]
-        return AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False, None, None, None, dead, add_mask)[0]
-    if hd > 64:
-        if isinstance(qkv, HeadImage):
-            raise ValueError("self_attention: head images hold 64-column heads")
-        if hd > 128:
-            return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p)[0]
-        if _twin(qkv) is not None:
-            raise ValueError("self_attention: a twin batch runs on head images only")
-        return AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False)[0]     # 128-column kernels: no maxima
-    if isinstance(qkv, HeadImage):             # the in-projection left a head image: the LDS-DMA kernels
+    image = isinstance(qkv, HeadImage)
+    route = _attn_route("self_attention", _head_width(d, n_head), image, not image and _twin(qkv) is not None,
+                        dead is not None or add_mask is not None, _mask_needs_autograd(add_mask), False)
+    if route == "algebra":
+        return masked_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], lens, n_head, causal, drop_p, dead,
+                                _finite_mask(add_mask))[0]
+    if route == "image":                       # the in-projection left a head image: the LDS-DMA kernels
         o_am = _amax_slots(qkv.device, True)
         twin = _twin_of(qkv.cells, lens)
         o = _twin_attach(SelfAttentionImgFn.apply(qkv.cells, qkv, lens, n_head, causal, drop_p, seed, o_am, twin), twin)
         o._ttts_amax = o_am
         return o
-    if _twin(qkv) is not None:
-        raise ValueError("self_attention: a twin batch runs on head images only")
-    am = _amax(qkv) if qkv.is_cuda else None
-    o_am = _amax_slots(qkv.device, True) if qkv.is_cuda else None
-    o, _ = AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False, am, None, o_am)
+    am = o_am = None                           # the 128-column kernels take no maxima and publish none
+    if route == "h3" and qkv.is_cuda:
+        am, o_am = _amax(qkv), _amax_slots(qkv.device, True)
+    o, _ = AttentionFn.apply(qkv, None, lens, n_head, causal, drop_p, seed, False, am, None, o_am, dead, add_mask)
     if o_am is not None:
         o._ttts_amax = o_am
     return o
@@ -2418,37 +2411,24 @@ def cross_attention(q, kv, lens, n_head: int, drop_p: float, seed: int, need_wei
     128-column kernels at any head_dim <= 128; wider heads go to `masked_attention`, which autograd differentiates anyway.
     Without it the weights are detached, as they always were."""
     d = q.shape[-1]
-    hd = _head_width(d, n_head)
-    if weights_grad and need_weights:
-        if isinstance(q, HeadImage) or isinstance(kv, HeadImage) or _twin(q) is not None:
-            raise ValueError("cross_attention: differentiable weights take fp32 operands (no head image, no twin batch)")
-        if hd > 128 or _mask_needs_autograd(add_mask):
-            return masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p, dead, _finite_mask(add_mask))
-        return AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, True, None, None, None, dead, add_mask, True)
-    if dead is not None or add_mask is not None:
-        if isinstance(q, HeadImage) or isinstance(kv, HeadImage) or _twin(q) is not None:
-            raise ValueError("cross_attention: a head image / twin batch takes length masks only")
-        if hd > 128 or _mask_needs_autograd(add_mask):
-            o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p, dead, _finite_mask(add_mask))
-            return o, (attn if need_weights else None)
-        return AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights, None, None, None, dead, add_mask)
-    if hd > 64:
-        if isinstance(q, HeadImage) or isinstance(kv, HeadImage):
-            raise ValueError("cross_attention: head images hold 64-column heads")
-        if hd > 128:
-            o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p)
-            return o, (attn if need_weights else None)
-        return AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights)     # 128-column kernels: no maxima
-    if isinstance(q, HeadImage) != isinstance(kv, HeadImage):
-        raise ValueError("cross_attention: q and kv must both be head images or both fp32")
-    if isinstance(q, HeadImage):
+    image = isinstance(q, HeadImage) or isinstance(kv, HeadImage)
+    weights_grad = bool(weights_grad and need_weights)
+    route = _attn_route("cross_attention", _head_width(d, n_head), image, not image and _twin(q) is not None,
+                        dead is not None or add_mask is not None, _mask_needs_autograd(add_mask), weights_grad)
+    if route == "algebra":
+        o, attn = masked_attention(q, kv[..., :d], kv[..., d:], lens, n_head, False, drop_p, dead, _finite_mask(add_mask))
+        return o, (attn if need_weights else None)
+    if route == "image":
+        if not (isinstance(q, HeadImage) and isinstance(kv, HeadImage)):
+            raise ValueError("cross_attention: q and kv must both be head images or both fp32")
         o_am = _amax_slots(q.device, True)
         o, attn = CrossAttentionImgFn.apply(q.cells, q, kv.cells, kv, lens, n_head, drop_p, seed, need_weights, o_am)
         o._ttts_amax = o_am
         return o, attn
-    q_am, kv_am = (_amax(q), _amax(kv)) if q.is_cuda else (None, None)
-    o_am = _amax_slots(q.device, True) if q.is_cuda else None
-    o, attn = AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights, q_am, kv_am, o_am)
+    q_am = kv_am = o_am = None                 # the 128-column kernels take no maxima and publish none
+    if route == "h3" and q.is_cuda:
+        q_am, kv_am, o_am = _amax(q), _amax(kv), _amax_slots(q.device, True)
+    o, attn = AttentionFn.apply(q, kv, lens, n_head, False, drop_p, seed, need_weights, q_am, kv_am, o_am, dead, add_mask, weights_grad)
     if o_am is not None:
         o._ttts_amax = o_am
     return o, attn
