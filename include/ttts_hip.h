@@ -73,6 +73,18 @@ typedef struct ttts_decode_state {
     int32_t flags;        /* 28: TTTS_DECODE_PER_ROW or 0; read by ttts_decode_frame_out_rows only */
 } ttts_decode_state;
 
+/* Attention window of one decoder layer's cross-attention at synthesis (ABI v21; 32 bytes, fields at fixed offsets), read by
+ * ttts_decode_attention_window when it runs: which heads are constrained, how far they see and which head moves the window
+ * are data, so one captured graph serves every window. */
+typedef struct ttts_decode_window {
+    int32_t back;         /*  0: keys behind the position a constrained head still sees (>= 0) */
+    int32_t ahead;        /*  4: keys ahead of it (>= 0) */
+    int32_t guide_head;   /*  8: the head whose largest in-window score becomes the next position; -1: none in this layer */
+    int32_t pad;          /* 12 */
+    uint64_t head_mask;   /* 16: bit h set: head h is constrained */
+    int64_t reserved;     /* 24 */
+} ttts_decode_window;
+
 const char* ttts_last_error(void);
 int ttts_abi_version(void);
 
@@ -735,6 +747,28 @@ int ttts_decode_attention_rows(const float* q, int64_t ldq, const float* k, cons
                                const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
                                int max_keys, const int64_t* row_end, float* map, int64_t map_ld_head, int64_t map_ld_row,
                                int map_rows, const ttts_decode_state* st, void* stream);
+/* ---- ABI v21: an attention window on the cross-attention of batched synthesis (decode.hip) ---------------------------------
+ * ttts_decode_attention_rows with, per utterance, a position that a guide head moves from frame to frame and a window around
+ * it that the constrained heads cannot see out of: the windowed inference of attention TTS toolkits.  The reference has no
+ * such mode (its `inference`, model/model.py:323-394, attends to every phoneme below the length at every frame); what this
+ * restates is torch's MHA softmax (torch/nn/functional.py multi_head_attention_forward) under an additive -inf mask on the keys
+ * outside  max(0, c - back) <= j <= min(len - 1, c + ahead)  (both ends inclusive) for the heads in win->head_mask.
+ *   win: this layer's window struct, on the device, 8-byte aligned.  pos: int32 positions, row b at pos + b * ld_pos; it must hold
+ *   t_end - 1 entries per row.  The centre c of frame t is pos[b, t - 2], and 0 at t = 1 (whatever pos holds then); a centre
+ *   outside [0, len) is clamped into it, so a window always holds a key; a struct with a negative back or ahead makes the
+ *   launch do nothing.  After the softmax the head win->guide_head (-1: none)
+ *   writes pos[b, t - 1] = the key with its largest score among those it sees, the lowest one on equal scores: every layer of
+ *   a frame reads the entry of the frame before, so there is no read-write race within a frame and pos needs no reset.
+ * Key blocks that do not meet a constrained head's window return before any K/V load; keys outside it are not loaded; with a
+ * map its row is exactly 0 outside the window up to max_keys.  A head that is not constrained, and every head under a window
+ * that covers all keys, gets bit for bit what ttts_decode_attention_rows gives; an ended row writes neither out, map nor pos.
+ * lens, row_end, win and pos are required; H <= 64.  The workspace is that of ttts_decode_attention_workspace_bytes (the
+ * blocks' first-maximum keys use a slot it already has). */
+int ttts_decode_attention_window(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
+                                 const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H,
+                                 int head_dim, int max_keys, const int64_t* row_end, float* map, int64_t map_ld_head,
+                                 int64_t map_ld_row, int map_rows, const ttts_decode_window* win, int32_t* pos, int64_t ld_pos,
+                                 const ttts_decode_state* st, void* stream);
 /* x (outer, T, C) contiguous: rows t >= lens[o / group] of slice o := 0 (lens int64 on the device, clamped to [0, T]; group
  * slices share one length: the heads of an attention map).  The frames behind each utterance's end in the outputs of a batched
  * synthesis, and in the post-net's input and every layer's output (a convolution over a zero-padded batch does not keep them

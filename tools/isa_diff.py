@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Compare two `hipcc -S` outputs (files, or directories of *.s matched by name) kernel by kernel.
 
-    python tools/isa_diff.py OLD NEW [--rename REGEX=REPLACEMENT ...]
+    python tools/isa_diff.py OLD NEW [--rename REGEX=REPLACEMENT ...] [--common]
 
 --rename rewrites the names of NEW's kernels (re.sub, in the order given) before they are matched with OLD's: for a kernel whose
 code is meant to be the same but whose mangled name moved, e.g. a template that gained a defaulted argument.
+--common compares the kernels both sides have and only lists the others: for a change that adds kernels and must leave the
+existing ones alone.
 
 Per kernel: VGPR / AGPR / SGPR counts, scratch and LDS bytes, and every opcode whose count differs.  Exit status 1 when a
 resource differs, a kernel is missing, or an opcode outside the scalar ALU differs in count; scalar-ALU differences (s_*
@@ -48,7 +50,7 @@ def kernels(path):
     return {k: (res[k], ops[k]) for k in res}, no_register
 
 
-def main(old, new, renames=()):
+def main(old, new, renames=(), common=False):
     (a, na), (b, nb) = kernels(old), kernels(new)
     for pattern, repl in renames:
         renamed = {re.sub(pattern, repl, name): v for name, v in b.items()}
@@ -59,8 +61,8 @@ def main(old, new, renames=()):
     bad = 0
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
-            print(f"{name}\n  MISSING in {'old' if name not in a else 'new'}")
-            bad += 1
+            print(f"{name}\n  MISSING in {'old' if name not in a else 'new'}" + ("  (not compared: --common)" if common else ""))
+            bad += not common
             continue
         (ra, oa), (rb, ob) = a[name], b[name]
         diff = {o: (oa[o], ob[o]) for o in set(oa) | set(ob) if oa[o] != ob[o]}
@@ -83,6 +85,8 @@ if __name__ == "__main__":
             sys.exit(__doc__)
         renames.append(tuple(args[i + 1].split("=", 1)))
         del args[i:i + 2]
+    common = "--common" in args
+    args = [x for x in args if x != "--common"]
     if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(args[0], args[1], renames))
+    sys.exit(main(args[0], args[1], renames, common))

@@ -19,6 +19,14 @@ ends), and at B = --maps-at the same with alignment maps.  Reports the frames pr
 mel_lens.sum() / (B x 1499) -- the bound a call that skipped all finished work at no cost would reach -- and the achieved
 time ratio.  --save-head / --load-head --one-call: fit once, then run exactly one `synthesize` call in a process of its own
 (for a kernel trace of one call).
+
+    python tools/synthesis_bench.py --ragged --window BACK,AHEAD[,LAYER,HEAD] [--configs base:16,base:64] [--reps 5] [--out FILE]
+
+The same set-up, timing `synthesize(window=AttentionWindow((LAYER, HEAD), BACK, AHEAD))` against `synthesize(window=None)` at
+threshold 0.5 and at 2.0, alternating the calls within every repetition in one process (guide (0, 0) unless given: a model with
+random weights has no diagonal head, and what the window costs does not depend on which head moves it).  The stop head is the
+one fitted on the unwindowed frames, so the windowed call's ends are its own: both calls' frames are reported, and the ratio at
+threshold 2.0 (1499 frames either way) is the like-for-like one.
 """
 from __future__ import annotations
 
@@ -36,7 +44,7 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from transformertts_amd.model import TransformerTTS  # noqa: E402
-from transformertts_amd.synthesis import Synthesizer  # noqa: E402
+from transformertts_amd.synthesis import AttentionWindow, Synthesizer  # noqa: E402
 from transformertts_amd.workload import model_config, synth_batch  # noqa: E402
 
 TP, MAX_LEN, STOP = 100, 1500, 2.0
@@ -110,7 +118,30 @@ def _alternating(fns: dict, reps: int) -> dict:
     return times
 
 
-def run_ragged(cfg_name: str, B: int, reps: int, maps: bool, save_head, load_head, one_call: bool) -> dict:
+def _window_record(rec, synth, ph, pl, window, reps):
+    """adds the windowed timings of --window to a --ragged record"""
+    fns = {"synthesize_full": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=STOP),
+           "window_full": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=STOP, window=window),
+           "synthesize_ragged": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5),
+           "window_ragged": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5, window=window)}
+    out = fns["window_ragged"]()
+    pos = out["attention_positions"]
+    times = _alternating(fns, reps)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for k, v in times.items():
+        rec[k + "_ms"] = round(med[k] * 1e3, 2)
+        rec[k + "_ms_all"] = [round(x * 1e3, 2) for x in v]
+    rec.update({"window": {"guide": list(window.guide), "back": window.back, "ahead": window.ahead},
+                "window_ragged_frames_decoded": int(out["mel_lens"].max()),
+                "window_ragged_frames_produced": int(out["mel_lens"].sum()),
+                "window_last_positions": [int(pos[b, int(n) - 1]) for b, n in enumerate(out["mel_lens"].tolist())],
+                "window_over_none_full": round(med["window_full"] / med["synthesize_full"], 4),
+                "window_over_none_ragged": round(med["window_ragged"] / med["synthesize_ragged"], 4),
+                "captures": synth.captures, "static_bytes_per_shape": sum(synth.shape_bytes().values())})
+    return rec
+
+
+def run_ragged(cfg_name: str, B: int, reps: int, maps: bool, save_head, load_head, one_call: bool, window=None) -> dict:
     torch.manual_seed(0)
     cfg = model_config(cfg_name)
     m = TransformerTTS(**cfg, device="cuda").to("cuda").eval()
@@ -143,6 +174,10 @@ def run_ragged(cfg_name: str, B: int, reps: int, maps: bool, save_head, load_hea
     for b, n in enumerate(lens.tolist()):
         assert torch.equal(out["pred_melspec"][b, :n], free["pred_melspec"][b, :n]), b
         assert bool((out["pred_melspec"][b, n:] == 0).all()) and bool((out["post_melspec"][b, n:] == 0).all()), b
+    if window is not None:
+        rec = {"config": cfg_name, "B": B, "Tp": TP, "max_len": MAX_LEN, "reps": reps, "chunk": synth.chunk,
+               "mel_lens": sorted(lens.tolist()), "frames_decoded": int(lens.max()), "frames_produced": int(lens.sum())}
+        return _window_record(rec, synth, ph, pl, window, reps)
     fns = {"call_full": lambda: synth(ph, pl, max_len=MAX_LEN, stop_threshold=STOP),
            "synthesize_full": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=STOP),
            "synthesize_ragged": lambda: synth.synthesize(ph, pl, max_len=MAX_LEN, stop_threshold=0.5)}
@@ -182,9 +217,18 @@ def main():
     ap.add_argument("--save-head", default=None, help="--ragged: save the fitted stop head")
     ap.add_argument("--load-head", default=None, help="--ragged: use a saved stop head instead of probing and fitting")
     ap.add_argument("--one-call", action="store_true", help="--ragged --load-head: exactly one synthesize call, no timing")
+    ap.add_argument("--window", default=None, help="--ragged: BACK,AHEAD[,LAYER,HEAD]: time synthesize with this attention window "
+                                                   "against synthesize without one")
     a = ap.parse_args()
     if a.one_call and not (a.ragged and a.load_head):
         raise SystemExit("synthesis_bench: --one-call needs --ragged and --load-head")
+    window = None
+    if a.window is not None:
+        parts = a.window.split(",")
+        if not a.ragged or a.one_call or len(parts) not in (2, 4) or not all(x.strip().lstrip("-").isdigit() for x in parts):
+            raise SystemExit("synthesis_bench: --window BACK,AHEAD[,LAYER,HEAD] goes with --ragged (and not with --one-call)")
+        v = [int(x) for x in parts]
+        window = AttentionWindow(guide=(v[2], v[3]) if len(v) == 4 else (0, 0), back=v[0], ahead=v[1])
     if not torch.cuda.is_available():
         raise SystemExit("synthesis_bench: needs the HIP device")
     if a.ragged and a.configs == ap.get_default("configs"):
@@ -193,7 +237,7 @@ def main():
     for item in a.configs.split(","):
         name, B = item.split(":")
         if a.ragged:
-            rec = run_ragged(name, int(B), a.reps, int(B) == a.maps_at, a.save_head, a.load_head, a.one_call)
+            rec = run_ragged(name, int(B), a.reps, int(B) == a.maps_at, a.save_head, a.load_head, a.one_call, window)
         else:
             rec = run(name, int(B), a.reps, a.skip_inference)
         print(json.dumps(rec), flush=True)

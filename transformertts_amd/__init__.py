@@ -5,11 +5,14 @@ Drop-in for the reference's `model` package surface:
 Host code is Python on PyTorch-ROCm (memory, streams, autograd graph, torch.distributed); every
 arithmetic step of the path runs in hand-written HIP kernels behind the C ABI of include/ttts_hip.h.
 """
-__all__ = ["model", "ops", "extract_durations", "teacher_durations"]
+__all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionWindow"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
     if name in ("extract_durations", "teacher_durations"):
         from . import alignment
         return getattr(alignment, name)
+    if name == "AttentionWindow":   # the window of Synthesizer.synthesize(window=...)
+        from . import synthesis
+        return synthesis.AttentionWindow
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

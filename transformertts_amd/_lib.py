@@ -139,6 +139,7 @@ SIGNATURES = {
     "ttts_decode_frame_out_rows": (I, [P, P, P, P, P, P, L, P, L, I, I, I, P, P, P]),
     "ttts_decode_layernorm_rows": (I, [P, P, P, P, I, I, F, P, P, P]),
     "ttts_decode_attention_rows": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P, L, L, I, P, P]),
+    "ttts_decode_attention_window": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P, L, L, I, P, P, L, P, P]),
     "ttts_mask_rows": (I, [P, P, L, I, L, L, P]),
 }
 

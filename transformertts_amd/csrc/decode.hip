@@ -291,30 +291,86 @@ struct AttnMap {
     int rows;                // frames the planes hold: row t - 1 is written when t - 1 < rows
 };
 
-template <int HD, bool MAPS>
+// WIN (ttts_decode_attention_window): this layer's ttts_decode_window and the per-utterance positions.  A constrained head
+// (bit h of head_mask) sees keys [max(0, c - back), min(len - 1, c + ahead)] only, c = pos[b, t - 2] (0 at t = 1): the window
+// struct is read with the state and row_end; the centre's address needs t, so it is read behind the state, with lens[b].  A block
+// that does not meet the window returns before any K/V load, keys outside it are not loaded and score -inf like the keys past
+// the length.  The guide head's blocks also store the index of their first maximum key (workspace slot HD + 2).
+template <bool WIN>
+struct AttnWin {};
+template <>
+struct AttnWin<true> {
+    const ttts_decode_window* win;
+    int32_t* pos;            // (B, ld_pos): frame t reads pos[b, t - 2], the guide head's combine writes pos[b, t - 1]
+    long ld_pos;
+};
+
+// The centre of frame t: pos[b, t - 2], 0 at t = 1.  The load is unconditional (entry 0 stands in at t = 1 and is not used) and
+// every head issues it, next to the length: the one read that needs t then shares its round trip with lens[b].
+__device__ __forceinline__ long window_centre(const int32_t* pos, long ld_pos, int b, int64_t t) {
+    const int32_t v = pos[(long)b * ld_pos + (long)(t >= 2 ? t - 2 : 0)];
+    return t >= 2 ? (long)v : 0;
+}
+
+// keys [lo, hi] a constrained head sees around centre c (len >= 1): c is clamped into the keys, so the window is never empty
+__device__ __forceinline__ void window_range(const ttts_decode_window& wn, long c, long len, long& lo, long& hi) {
+    c = c < 0 ? 0 : (c > len - 1 ? len - 1 : c);
+    lo = c - (long)wn.back;
+    lo = lo < 0 ? 0 : lo;
+    hi = c + (long)wn.ahead;
+    hi = hi > len - 1 ? len - 1 : hi;
+}
+
+template <int HD, bool MAPS, bool WIN = false>
 __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
                                                                   const float* __restrict__ v, long ld_row, long ld_batch,
                                                                   const int64_t* __restrict__ lens, float* __restrict__ ws, int H,
                                                                   int nsplit, int max_keys, float scale,
                                                                   const int64_t* __restrict__ row_end, const AttnMap map,
-                                                                  const ttts_decode_state* st) {
+                                                                  const ttts_decode_state* st, const AttnWin<WIN> w) {
     constexpr int CH = HD / 16;               // float4 per lane
     constexpr int WS = HD + 4;                // workspace floats per block
     __shared__ float red_m[4], red_l[4];
     __shared__ float4 red_o[4][HD / 4];
+    __shared__ int red_i[4];                  // (WIN: first maximum key of each wave)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const bool ended = row_ended(row_end, st, b);
+    ttts_decode_window wn;
+    bool no_window = false;                   // a struct with a negative reach: the launch does nothing.  Being part of the first
+    if constexpr (WIN) {                      // branch is also what puts the struct's read into the scalar batch of the state
+        wn = *w.win;
+        no_window = (wn.back | wn.ahead) < 0;
+    }
     int64_t t;
-    if (decode_done(st, t) | ended) return;   // (uniform over the workgroup)
-    long len = lens != nullptr ? (long)lens[b] : (long)t;
+    if (decode_done(st, t) | ended | no_window) return;   // (uniform over the workgroup)
+    long len, centre = 0;
+    if constexpr (WIN) {                      // (lens is required: the length and the centre are one scalar batch)
+        len = (long)lens[b];
+        centre = window_centre(w.pos, w.ld_pos, b, t);
+    } else {
+        len = lens != nullptr ? (long)lens[b] : (long)t;
+    }
     len = len < (long)max_keys ? len : (long)max_keys;
     const int key0 = s * ATTN_KEYS;
-    if (key0 >= len) return;                  // (uniform over the workgroup)
+    if constexpr (!WIN) {
+        if (key0 >= len) return;              // (uniform over the workgroup)
+    }
     const int key = key0 + wave * 16 + (lane >> 2), sub = lane & 3;
+    bool live = key < len;
+    bool guide = false;
+    if constexpr (WIN) {
+        long lo, hi;                          // (selects, not a branch around the centre: its load stays next to the length's)
+        window_range(wn, centre, len, lo, hi);
+        const bool con = ((wn.head_mask >> h) & 1) & (len > 0);
+        lo = con ? lo : 0;
+        hi = con ? hi : len - 1;
+        if ((key0 >= len) | ((long)key0 > hi) | ((long)key0 + ATTN_KEYS - 1 < lo)) return;   // (uniform over the workgroup)
+        guide = h == wn.guide_head;
+        live = live && (long)key >= lo && (long)key <= hi;
+    }
     const long col = (long)h * HD + sub * (HD / 4);
     const float4* q4 = reinterpret_cast<const float4*>(q + (long)b * ldq + col);
-    const bool live = key < len;
     float4 kv[CH], vv[CH];
     const long kro = (long)b * ld_batch + (long)key * ld_row + col;
 #pragma unroll
@@ -334,6 +390,17 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const float* _
     sc = live ? sc : -INFINITY;
     const float wm = wave_max(sc);
     if (lane == 0) red_m[wave] = wm;
+    if constexpr (WIN) {
+        if (guide) {                          // lowest live key that holds the wave's maximum (a butterfly of minima: fixed order)
+            int cand = (live && sc == wm) ? key : 0x7fffffff;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const int other = __shfl_xor(cand, off, 64);
+                cand = other < cand ? other : cand;
+            }
+            if (lane == 0) red_i[wave] = cand;
+        }
+    }
     __syncthreads();
     const float mb = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));   // finite: key0 < len
     const float p = live ? expf(sc - mb) : 0.f;
@@ -374,35 +441,74 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const float* _
     if (threadIdx.x == 0) {
         out[HD] = mb;
         out[HD + 1] = ((red_l[0] + red_l[1]) + red_l[2]) + red_l[3];
+        if constexpr (WIN) {
+            if (guide) {                      // the waves hold ascending keys: the first wave at the block maximum wins a tie
+                const int idx = red_m[0] == mb ? red_i[0] : red_m[1] == mb ? red_i[1] : red_m[2] == mb ? red_i[2] : red_i[3];
+                out[HD + 2] = __int_as_float(idx);
+            }
+        }
     }
 }
 
 // one wave per (head, utterance): out = sum_s o_s e^(m_s - m) / sum_s l_s e^(m_s - m) over the blocks below the length
 // MAPS: map row t - 1, key j of block s = (its unnormalised weight * e^(m_s - m)) / l below the length, 0 from there to max_keys
-template <int HD, bool MAPS>
+// WIN: a constrained head walks the blocks that meet its window only (the others hold stale workspace); the guide head writes
+// pos[b, t - 1] = the first maximum key of the lowest block at the largest block maximum; MAPS zeroes every key outside the window
+template <int HD, bool MAPS, bool WIN = false>
 __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __restrict__ ws, const int64_t* __restrict__ lens,
                                                                  float* __restrict__ out, long ldo, int H, int nsplit, int max_keys,
                                                                  const int64_t* __restrict__ row_end, const AttnMap map,
-                                                                 const ttts_decode_state* st) {
+                                                                 const ttts_decode_state* st, const AttnWin<WIN> w) {
     constexpr int WS = HD + 4;
     const int lane = threadIdx.x, h = blockIdx.x, b = blockIdx.y;
     const bool ended = row_ended(row_end, st, b);
+    ttts_decode_window wn;
+    bool no_window = false;                   // (as in the partial kernel)
+    if constexpr (WIN) {
+        wn = *w.win;
+        no_window = (wn.back | wn.ahead) < 0;
+    }
     int64_t t;
-    if (decode_done(st, t) | ended) return;   // (uniform over the wave)
-    long len = lens != nullptr ? (long)lens[b] : (long)t;
+    if (decode_done(st, t) | ended | no_window) return;   // (uniform over the wave)
+    long len, centre = 0;
+    if constexpr (WIN) {                      // (as in the partial kernel)
+        len = (long)lens[b];
+        centre = window_centre(w.pos, w.ld_pos, b, t);
+    } else {
+        len = lens != nullptr ? (long)lens[b] : (long)t;
+    }
     len = len < (long)max_keys ? len : (long)max_keys;
     const int nblk = len > 0 ? (int)((len + ATTN_KEYS - 1) / ATTN_KEYS) : 0;
     const float* p = ws + ((long)b * H + h) * nsplit * WS;
+    int s_lo = 0, s_end = nblk;               // the blocks [s_lo, s_end) that hold this frame's partials
+    long lo = 0, hi = len - 1;                // the keys that carry weight
+    if constexpr (WIN) {                      // (selects, as in the partial kernel)
+        long wlo, whi;
+        window_range(wn, centre, len, wlo, whi);
+        const bool con = ((wn.head_mask >> h) & 1) & (len > 0);
+        lo = con ? wlo : lo;
+        hi = con ? whi : hi;
+        s_lo = con ? (int)(wlo / ATTN_KEYS) : s_lo;
+        s_end = con ? (int)(whi / ATTN_KEYS) + 1 : s_end;
+    }
     float m = -INFINITY;
-    for (int s = 0; s < nblk; ++s) m = fmaxf(m, p[s * WS + HD]);
+    for (int s = s_lo; s < s_end; ++s) m = fmaxf(m, p[s * WS + HD]);
+    if constexpr (WIN) {
+        if (h == wn.guide_head && lane == 0) {
+            int idx = 0;
+            for (int s = s_end - 1; s >= s_lo; --s)       // (descending: the lowest block at the maximum is the last one kept)
+                if (p[s * WS + HD] == m) idx = __float_as_int(p[s * WS + HD + 2]);
+            w.pos[(long)b * w.ld_pos + (long)(t - 1)] = idx;
+        }
+    }
     float l = 0.f, o0 = 0.f, o1 = 0.f;
-    for (int s = 0; s < nblk; ++s) {
+    for (int s = s_lo; s < s_end; ++s) {
         const float e = expf(p[s * WS + HD] - m);
         l = fmaf(p[s * WS + HD + 1], e, l);
         if (lane < HD) o0 = fmaf(p[s * WS + lane], e, o0);
         if (lane + 64 < HD) o1 = fmaf(p[s * WS + lane + 64], e, o1);
     }
-    const float inv = nblk > 0 ? 1.0f / l : 0.f;
+    const float inv = s_end > s_lo ? 1.0f / l : 0.f;
     float* orow = out + (long)b * ldo + (long)h * HD;
     if (lane < HD) orow[lane] = o0 * inv;
     if (lane + 64 < HD) orow[lane + 64] = o1 * inv;
@@ -413,7 +519,7 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
             const int key = s * ATTN_KEYS + lane;
             if (key >= max_keys) break;
             float a = 0.f;
-            if (s < nblk && key < len) a = (mrow[key] * expf(p[s * WS + HD] - m)) * inv;
+            if (s >= s_lo && s < s_end && (long)key >= lo && (long)key <= hi) a = (mrow[key] * expf(p[s * WS + HD] - m)) * inv;
             mrow[key] = a;
         }
     }
@@ -432,22 +538,33 @@ struct AttnArgs {
     const int64_t* row_end;
     AttnMap map;
     const ttts_decode_state* st;
+    const ttts_decode_window* win;   // ttts_decode_attention_window only: NULL selects the kernels without window code
+    int32_t* pos;
+    long ld_pos;
 };
 
-template <int HD, bool MAPS>
+template <int HD, bool MAPS, bool WIN>
 void launch_decode_attention_tm(const AttnArgs& a, hipStream_t stream) {
     const int ns = attn_nsplit(a.max_keys);
     const float scale = 1.0f / sqrtf((float)HD);
-    hipLaunchKernelGGL((decode_attn_partial_kernel<HD, MAPS>), dim3(ns, a.H, a.B), dim3(256), 0, stream, a.q, a.ldq, a.k, a.v,
-                       a.ld_row, a.ld_batch, a.lens, a.ws, a.H, ns, a.max_keys, scale, a.row_end, a.map, a.st);
-    hipLaunchKernelGGL((decode_attn_combine_kernel<HD, MAPS>), dim3(a.H, a.B), dim3(64), 0, stream, a.ws, a.lens, a.out, a.ldo,
-                       a.H, ns, a.max_keys, a.row_end, a.map, a.st);
+    AttnWin<WIN> w;
+    if constexpr (WIN) w = AttnWin<true>{a.win, a.pos, a.ld_pos};
+    hipLaunchKernelGGL((decode_attn_partial_kernel<HD, MAPS, WIN>), dim3(ns, a.H, a.B), dim3(256), 0, stream, a.q, a.ldq, a.k, a.v,
+                       a.ld_row, a.ld_batch, a.lens, a.ws, a.H, ns, a.max_keys, scale, a.row_end, a.map, a.st, w);
+    hipLaunchKernelGGL((decode_attn_combine_kernel<HD, MAPS, WIN>), dim3(a.H, a.B), dim3(64), 0, stream, a.ws, a.lens, a.out, a.ldo,
+                       a.H, ns, a.max_keys, a.row_end, a.map, a.st, w);
 }
 
 template <int HD>
 void launch_decode_attention_t(const AttnArgs& a, hipStream_t stream) {
-    if (a.map.p != nullptr) launch_decode_attention_tm<HD, true>(a, stream);
-    else launch_decode_attention_tm<HD, false>(a, stream);
+    if (a.win != nullptr) {
+        if (a.map.p != nullptr) launch_decode_attention_tm<HD, true, true>(a, stream);
+        else launch_decode_attention_tm<HD, false, true>(a, stream);
+    } else if (a.map.p != nullptr) {
+        launch_decode_attention_tm<HD, true, false>(a, stream);
+    } else {
+        launch_decode_attention_tm<HD, false, false>(a, stream);
+    }
 }
 
 int check_decode_attention(const AttnArgs& a, int head_dim, size_t ws_bytes, const char* what) {
@@ -654,7 +771,7 @@ int ttts_decode_attention(const float* q, int64_t ldq, const float* k, const flo
                           const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H, int head_dim,
                           int max_keys, const ttts_decode_state* st, void* stream) {
     const AttnArgs a{q, k, v, (long)ldq, (long)ld_row, (long)ld_batch, lens, out, (long)ldo, ws, B, H, max_keys, nullptr,
-                     AttnMap{nullptr, 0, 0, 0}, st};
+                     AttnMap{nullptr, 0, 0, 0}, st, nullptr, nullptr, 0};
     const int rc = check_decode_attention(a, head_dim, ws_bytes, "decode_attention");
     if (rc != TTTS_OK) return rc;
     return launch_decode_attention(a, head_dim, (hipStream_t)stream, "decode_attention");
@@ -665,7 +782,7 @@ int ttts_decode_attention_rows(const float* q, int64_t ldq, const float* k, cons
                                int max_keys, const int64_t* row_end, float* map, int64_t map_ld_head, int64_t map_ld_row,
                                int map_rows, const ttts_decode_state* st, void* stream) {
     const AttnArgs a{q, k, v, (long)ldq, (long)ld_row, (long)ld_batch, lens, out, (long)ldo, ws, B, H, max_keys, row_end,
-                     AttnMap{map, (long)map_ld_head, (long)map_ld_row, map_rows}, st};
+                     AttnMap{map, (long)map_ld_head, (long)map_ld_row, map_rows}, st, nullptr, nullptr, 0};
     TTTS_REQUIRE(row_end, "decode_attention_rows: null pointer (row_end)");
     const int rc = check_decode_attention(a, head_dim, ws_bytes, "decode_attention_rows");
     if (rc != TTTS_OK) return rc;
@@ -673,6 +790,28 @@ int ttts_decode_attention_rows(const float* q, int64_t ldq, const float* k, cons
                  "decode_attention_rows: map of %d rows, ld_row=%ld ld_head=%ld (rows >= 1, ld_row >= max_keys=%d, ld_head >= "
                  "rows * ld_row)", map_rows, (long)map_ld_row, (long)map_ld_head, max_keys);
     return launch_decode_attention(a, head_dim, (hipStream_t)stream, "decode_attention_rows");
+}
+
+int ttts_decode_attention_window(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld_row, int64_t ld_batch,
+                                 const int64_t* lens, float* out, int64_t ldo, float* ws, size_t ws_bytes, int B, int H,
+                                 int head_dim, int max_keys, const int64_t* row_end, float* map, int64_t map_ld_head,
+                                 int64_t map_ld_row, int map_rows, const ttts_decode_window* win, int32_t* pos, int64_t ld_pos,
+                                 const ttts_decode_state* st, void* stream) {
+    const AttnArgs a{q, k, v, (long)ldq, (long)ld_row, (long)ld_batch, lens, out, (long)ldo, ws, B, H, max_keys, row_end,
+                     AttnMap{map, (long)map_ld_head, (long)map_ld_row, map_rows}, st, win, pos, (long)ld_pos};
+    TTTS_REQUIRE(row_end, "decode_attention_window: null pointer (row_end)");
+    TTTS_REQUIRE(lens, "decode_attention_window: null pointer (lens)");
+    TTTS_REQUIRE(win, "decode_attention_window: null pointer (win)");
+    TTTS_REQUIRE(pos, "decode_attention_window: null pointer (pos)");
+    const int rc = check_decode_attention(a, head_dim, ws_bytes, "decode_attention_window");
+    if (rc != TTTS_OK) return rc;
+    TTTS_REQUIRE(H <= 64, "decode_attention_window: H=%d heads (head_mask holds 64)", H);
+    TTTS_REQUIRE(ld_pos >= 1 && ((uintptr_t)win & 7) == 0 && ((uintptr_t)pos & 3) == 0,
+                 "decode_attention_window: ld_pos=%ld (>= 1), win 8-byte and pos 4-byte aligned", (long)ld_pos);
+    TTTS_REQUIRE(map == nullptr || (map_rows >= 1 && map_ld_row >= max_keys && map_ld_head >= (int64_t)map_rows * map_ld_row),
+                 "decode_attention_window: map of %d rows, ld_row=%ld ld_head=%ld (rows >= 1, ld_row >= max_keys=%d, ld_head >= "
+                 "rows * ld_row)", map_rows, (long)map_ld_row, (long)map_ld_head, max_keys);
+    return launch_decode_attention(a, head_dim, (hipStream_t)stream, "decode_attention_window");
 }
 
 int ttts_mask_rows(float* x, const int64_t* lens, int64_t outer, int group, int64_t T, int64_t C, void* stream) {

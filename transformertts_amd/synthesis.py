@@ -30,11 +30,21 @@ first time it is needed: `__call__`'s (the entry points without per-row state: r
 `__call__` does not pay), `synthesize`'s, and `synthesize(alignments=True)`'s, whose cross-attention kernels are the
 map-writing variant; the map buffers are allocated with that capture.  Within a method, `max_len`, the threshold and where the
 rows stop are data: they never cause a capture.
+
+`synthesize(..., window=AttentionWindow(guide=(layer, head), back=1, ahead=3))` is the attention window that attention-TTS
+engines decode with: every utterance keeps a position, the phoneme the guide head attended at the previous frame, and the
+constrained heads' cross-attention sees only `back` phonemes behind and `ahead` phonemes ahead of it.  The positions live in a
+(B, cap) device array the guide head's kernel writes one entry of per frame, and the window, the guide and the selection of
+heads are a 32-byte struct per layer that the call copies next to the state reset: they are data too, so one more chunk graph
+per shape (and one for the map-writing kernels) serves every `AttentionWindow`.
 """
 from __future__ import annotations
 
+import numbers
 from collections import OrderedDict
 from ctypes import c_void_p
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -45,6 +55,23 @@ _TP_ROUND = 64
 _CAP_ROUND = 256
 _ACT_NONE, _ACT_RELU = 0, 1
 _PER_ROW = 1                        # TTTS_DECODE_PER_ROW
+
+
+_WINDOW_MODES = ("win", "winmaps")
+_I32_MAX = 2 ** 31 - 1
+
+
+@dataclass(frozen=True)
+class AttentionWindow:
+    """The attention window of `Synthesizer.synthesize(window=...)`.  `guide`: the (decoder layer, head) whose largest
+    in-window score at a frame becomes the utterance's position for the next frame.  A constrained head sees the keys
+    max(0, position - back) .. min(phoneme_len - 1, position + ahead), both inclusive; `layers` / `heads` select the constrained
+    ones as `GuidedAttentionLoss(layers=..., heads=...)` does (None = all, else the indices), and the guide must be among them."""
+    guide: Tuple[int, int]
+    back: int = 1
+    ahead: int = 3
+    layers: Optional[Sequence[int]] = None
+    heads: Optional[Sequence[int]] = None
 
 
 def _up(x: int, m: int) -> int:
@@ -82,6 +109,8 @@ class _Shape:
         self.ws_bytes = max(lib.ttts_decode_attention_workspace_bytes(B, H, d // H, cap),
                             lib.ttts_decode_attention_workspace_bytes(B, H, d // H, Tp_pad))
         self.ws = torch.zeros(max(self.ws_bytes // 4, 4), **f32)
+        self.win = torch.zeros(4 * len(layers), dtype=torch.int64, device=dev)     # one ttts_decode_window (32 bytes) per layer
+        self.pos = torch.zeros(B, cap, dtype=torch.int32, device=dev)        # attention-window positions, entry t - 1 per frame t
         self.maps = None                                                     # per layer (B, H, cap, Tp_pad), once asked for
         self._map_shape = (B, H, cap, Tp_pad)
         self.drop_graphs()
@@ -95,7 +124,7 @@ class _Shape:
             self.maps = [torch.zeros(*self._map_shape, dtype=torch.float32, device=self.state.device) for _ in range(n_layers)]
 
     def nbytes(self) -> int:
-        ts = [self.state, self.ys, self.stop, self.h, self.tmp, self.q, self.ctx, self.ffn, self.lens, self.ws]
+        ts = [self.state, self.ys, self.stop, self.h, self.tmp, self.q, self.ctx, self.ffn, self.lens, self.ws, self.win, self.pos]
         return sum(t.numel() * t.element_size() for t in ts + self.cache + self.memkv + (self.maps or []))
 
 
@@ -115,7 +144,8 @@ class Synthesizer:
         self._weights_sig = None
         self._side = None
         self.captures = 0            # chunk graphs captured so far (per shape: the first __call__, the first synthesize, the
-        #                              first synthesize with alignments; and again after its weights moved)
+        #                              first synthesize with alignments, the first with a window, the first with a window and
+        #                              alignments; and again after its weights moved)
         self.recaptures = 0          # times moved parameter storage dropped the captured graphs
 
     @property
@@ -151,6 +181,53 @@ class Synthesizer:
             raise ValueError(f"Synthesizer: `phoneme` must be (B, Tp), got {tuple(phoneme.shape)}")
         if tuple(phoneme_lens.shape) != (phoneme.size(0),):
             raise ValueError(f"Synthesizer: `phoneme_lens` must be (B,) = ({phoneme.size(0)},), got {tuple(phoneme_lens.shape)}")
+
+    def _check_window(self, window):
+        """-> per decoder layer (back, ahead, guide head or -1, head mask), or raises: host logic only"""
+        if not isinstance(window, AttentionWindow):
+            raise ValueError(f"Synthesizer: `window` must be an AttentionWindow or None, got {type(window).__name__}")
+        layers = list(self.model.decoder.layers)
+        if layers and layers[0].self_attn.num_heads > 64:        # (the head mask of ttts_decode_window holds 64)
+            raise ValueError(f"Synthesizer: an attention window takes at most 64 decoder heads, the model has "
+                             f"{layers[0].self_attn.num_heads}")
+        _check_structure(self.model)
+        n_layers, H = len(layers), layers[0].self_attn.num_heads
+
+        def integer(x):
+            return isinstance(x, numbers.Integral) and not isinstance(x, bool)
+
+        for name, v in (("back", window.back), ("ahead", window.ahead)):
+            if not integer(v) or v < 0:
+                raise ValueError(f"Synthesizer: `window.{name}` must be a non-negative integer, got {v!r}")
+        sel = {}
+        for name, v, n in (("layers", window.layers, n_layers), ("heads", window.heads, H)):
+            if v is None:
+                sel[name] = list(range(n))
+                continue
+            if isinstance(v, (str, bytes)) or not hasattr(v, "__iter__"):
+                raise ValueError(f"Synthesizer: `window.{name}` must be None or a sequence of indices, got {v!r}")
+            idx = list(v)
+            if not all(integer(i) for i in idx):
+                raise ValueError(f"Synthesizer: `window.{name}` must hold integers, got {idx!r}")
+            idx = [int(i) for i in idx]
+            if len(set(idx)) != len(idx):
+                raise ValueError(f"Synthesizer: `window.{name}` holds an index twice: {idx!r}")
+            if any(i < 0 or i >= n for i in idx):
+                raise ValueError(f"Synthesizer: `window.{name}` = {idx!r} out of range (the decoder has {n})")
+            sel[name] = sorted(idx)
+        g = window.guide
+        if isinstance(g, (str, bytes)) or not hasattr(g, "__len__") or len(g) != 2 or not all(integer(i) for i in g):
+            raise ValueError(f"Synthesizer: `window.guide` must be a (decoder layer, head) pair of integers, got {g!r}")
+        gl, gh = int(g[0]), int(g[1])
+        if not (0 <= gl < n_layers and 0 <= gh < H):
+            raise ValueError(f"Synthesizer: `window.guide` = ({gl}, {gh}) is outside the model ({n_layers} decoder layers of {H} "
+                             f"heads)")
+        if gl not in sel["layers"] or gh not in sel["heads"]:
+            raise ValueError(f"Synthesizer: `window.guide` = ({gl}, {gh}) is not among the constrained (layer, head)s "
+                             f"(layers {sel['layers']}, heads {sel['heads']})")
+        mask = sum(1 << h for h in sel["heads"])
+        back, ahead = min(int(window.back), _I32_MAX), min(int(window.ahead), _I32_MAX)
+        return [(back, ahead, gh if i == gl else -1, mask if i in sel["layers"] else 0) for i in range(n_layers)]
 
     # ------------------------------------------------------------------------------------------------------ weights
     def _weight_tensors(self):
@@ -190,7 +267,8 @@ class Synthesizer:
     def _frame_calls(self, sh: _Shape, mode: str):
         """the launch sequence of one frame: [(entry point, arguments without the stream)].  `mode` "call": the entry points
         without per-row state (no row ever ends); "rows": the *_rows entry points on the shape's row_end; "maps": those, with
-        cross-attention also writing row t - 1 of every layer's alignment map"""
+        cross-attention also writing row t - 1 of every layer's alignment map; "win" / "winmaps": as "rows" / "maps" with the
+        cross-attention of every layer on ttts_decode_attention_window (which heads of which layers it constrains is data)"""
         lib = _lib.load()
         m = self.model
         layers = list(m.decoder.layers)
@@ -222,7 +300,10 @@ class Synthesizer:
         for i, (l, cache, mkv) in enumerate(zip(layers, sh.cache, sh.memkv)):
             sa, ca = l.self_attn, l.multihead_attn
             no_map = (*re, None, 0, 0, 0) if rows else ()
-            amap = (*re, _ptr(sh.maps[i]), cap * sh.Tp_pad, sh.Tp_pad, cap) if mode == "maps" else no_map
+            amap = (*re, _ptr(sh.maps[i]), cap * sh.Tp_pad, sh.Tp_pad, cap) if mode in ("maps", "winmaps") else no_map
+            f_cross, win = f_att, ()
+            if mode in _WINDOW_MODES:
+                f_cross, win = lib.ttts_decode_attention_window, (c_void_p(sh.win.data_ptr() + 32 * i), c_void_p(sh.pos.data_ptr()), cap)
             # in-projection: q to `q`, the K/V columns straight into row t - 1 of this layer's cache
             calls.append((f_lin, (h, d, 0, _ptr(sa.in_proj_weight), _ptr(sa.in_proj_bias), None, 0, q, d, 0, _ptr(cache),
                                   cap * 2 * d, 2 * d, d, B, 3 * d, d, _ACT_NONE, *re, st)))
@@ -231,8 +312,8 @@ class Synthesizer:
             calls.append(linear(ctx, d, sa.out_proj.weight, sa.out_proj.bias, tmp, d, res=h))
             calls.append(norm(l.norm1))
             calls.append(linear(h, d, ca.in_proj_weight, ca.in_proj_bias, q, d))          # rows 0 .. d - 1: the q projection
-            calls.append((f_att, (q, d, _ptr(mkv), _ptr(mkv, d), 2 * d, sh.Tp_pad * 2 * d, _ptr(sh.lens), ctx, d, ws, sh.ws_bytes,
-                                  B, H, hd, sh.Tp_pad, *amap, st)))
+            calls.append((f_cross, (q, d, _ptr(mkv), _ptr(mkv, d), 2 * d, sh.Tp_pad * 2 * d, _ptr(sh.lens), ctx, d, ws, sh.ws_bytes,
+                                    B, H, hd, sh.Tp_pad, *amap, *win, st)))
             calls.append(linear(ctx, d, ca.out_proj.weight, ca.out_proj.bias, tmp, d, res=h))
             calls.append(norm(l.norm2))
             calls.append(linear(h, d, l.linear1.weight, l.linear1.bias, ffn, d_ffn, act=_ACT_RELU))
@@ -253,9 +334,9 @@ class Synthesizer:
         return int(v[0]), int(v[2])
 
     # ------------------------------------------------------------------------------------------------------ the call
-    def _decode(self, phoneme, phoneme_lens, max_len: int, stop_threshold: float, mode: str):
+    def _decode(self, phoneme, phoneme_lens, max_len: int, stop_threshold: float, mode: str, window=None):
         """encoder, memory K/V, then the chunk graph of `mode` until the state says the decoding has ended: (shape, frames
-        decoded)"""
+        decoded).  `window`: the per-layer structs of _check_window for the window modes"""
         m = self.model
         m.eval()
         self._follow_weights()
@@ -277,7 +358,13 @@ class Synthesizer:
         host.view(torch.float32)[6] = float(stop_threshold)
         host.view(torch.int32)[7] = _PER_ROW if mode != "call" else 0
         sh.state.copy_(host)
-        if mode == "maps":
+        if window is not None:
+            whost = torch.zeros(sh.win.numel(), dtype=torch.int64)          # ttts_decode_window per layer
+            for i, (back, ahead, guide_head, mask) in enumerate(window):
+                whost.view(torch.int32)[8 * i:8 * i + 3] = torch.tensor([back, ahead, guide_head], dtype=torch.int32)
+                whost[4 * i + 2] = mask - (1 << 64) if mask >= 1 << 63 else mask
+            sh.win.copy_(whost)
+        if mode in ("maps", "winmaps"):
             sh.alloc_maps(len(layers))
         if sh.calls.get(mode) is None:
             sh.calls[mode] = self._frame_calls(sh, mode)
@@ -318,19 +405,33 @@ class Synthesizer:
 
     @torch.no_grad()
     def synthesize(self, phoneme: torch.Tensor, phoneme_lens: torch.Tensor, max_len: int = 1500, stop_threshold: float = 0.5,
-                   alignments: bool = False) -> dict:
+                   alignments: bool = False, window: Optional[AttentionWindow] = None) -> dict:
         """Every utterance at its own length.  Row b ends at its first frame t (1-based) with sigmoid(stop[b, t - 1]) >=
         `stop_threshold` -- that frame is kept -- or at `max_len` - 1; the call ends when every row has.  Returns `pred_melspec`,
         `post_melspec` (B, T, n_mels), `pred_stop` (B, T, 1) with T = mel_lens.max(), `mel_lens` (B,) int64 on the device, and
         with `alignments=True` one (B, heads, T, Tp) cross-attention map per decoder layer.  Everything at frame >= mel_lens[b]
         of row b is exactly 0; a row's frames before its end are bit for bit those of `__call__` for that row, and its
-        `post_melspec` is the post-net of its own frames (the rows behind each end are zeroed between the post-net's layers)."""
+        `post_melspec` is the post-net of its own frames (the rows behind each end are zeroed between the post-net's layers).
+
+        `window`: None, or an `AttentionWindow`.  Utterance b then carries a position, 0 at the first frame; at every frame the
+        constrained (layer, head)s take their cross-attention softmax over the keys max(0, position - back) ..
+        min(phoneme_lens[b] - 1, position + ahead) only, and the guide's key with the largest score among those (the lowest
+        one on equal scores) is the position every layer of the next frame uses.  Every other head, and self-attention, are
+        what they are without a window.  The call also returns `attention_positions` (B, T) int64 on the device: entry [b, f] is
+        the position after frame f + 1 (1-based), -1 at f >= mel_lens[b]; with `alignments=True` the maps of constrained heads
+        are exactly 0 outside each frame's window and their rows sum to 1.  A guide is a (layer, head) whose map is diagonal:
+        take `extract_durations(...)['choice']` (or what `teacher_durations(...)` chose) on a few utterances of the model."""
         if not isinstance(alignments, bool):
             raise ValueError(f"Synthesizer: `alignments` must be a bool, got {type(alignments).__name__}")
+        structs = self._check_window(window) if window is not None else None
         self._check_call(phoneme, phoneme_lens, max_len)
         m = self.model
         max_len = int(max_len)
-        sh, n = self._decode(phoneme, phoneme_lens, max_len, stop_threshold, "maps" if alignments else "rows")
+        if structs is None:
+            mode = "maps" if alignments else "rows"
+        else:
+            mode = "winmaps" if alignments else "win"
+        sh, n = self._decode(phoneme, phoneme_lens, max_len, stop_threshold, mode, structs)
         B, Tp = phoneme.shape
         row_end = sh.state[4:4 + B]
         mel_lens = torch.where(row_end > 0, row_end, torch.full_like(row_end, max_len - 1))
@@ -343,6 +444,10 @@ class Synthesizer:
         out = {'pred_melspec': pred, 'post_melspec': post, 'pred_stop': stops, 'mel_lens': mel_lens}
         if alignments:
             out['alignments'] = [_mask_rows(a[:, :, :n, :Tp].clone(), mel_lens) for a in sh.maps]
+        if structs is not None:
+            frames = torch.arange(n, device=mel_lens.device).unsqueeze(0)
+            pos = sh.pos[:, :n].to(torch.int64)
+            out['attention_positions'] = torch.where(frames < mel_lens.unsqueeze(1), pos, torch.full_like(pos, -1))
         return out
 
 
