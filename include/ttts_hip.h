@@ -558,6 +558,41 @@ size_t ttts_alignment_mas_workspace_bytes(int B, int Tm, int Tp);
 int ttts_alignment_mas(const float* const* maps, int L, int64_t ld_row, int64_t ld_head, int64_t ld_batch, const int64_t* choice,
                        const int64_t* phoneme_lens, const int64_t* melspec_lens, int B, int H, int Tm, int Tp, void* ws,
                        size_t ws_bytes, int64_t* durations, uint8_t* valid, void* stream);
+/* ---- dynamic time warping between two ragged batches of feature sequences (ABI v22; dtw.hip): the number that compares a
+ * synthesised mel with its recording, whose lengths never agree -- mel-DTW on log-mels, MCD-DTW on mel-cepstra.  In torch:
+ * `torch.cdist(x, y, p=1)` (or p=2) for the cells, then a Python loop over the Tx + Ty - 1 anti-diagonals of
+ * `torch.minimum(torch.minimum(D[i-1, j-1], D[i-1, j]), D[i, j-1])` with host control and a host loop for the path: thousands of
+ * launches a batch, not capturable.  Here: two launches, every decision on the device, nothing read back, no atomics, fp32
+ * throughout, fixed summation order: the call captures into a HIP graph and repeats bit for bit, and row b's result depends on
+ * neither the other rows nor Tx / Ty beyond its own lengths.
+ * Element (b, i, k) of x is x[b * ldx_batch + i * ldx_row + k] (strides in floats, unit channel stride, dword loads, no alignment
+ * asked), y alike; n_b = x_lens[b] clamped to [0, Tx], m_b = y_lens[b] clamped to [0, Ty] (int64, device).  Nothing at row >= n_b
+ * of x or row >= m_b of y is ever loaded.
+ *   cell cost   TTTS_DTW_L1: c[i][j] = sum_k |x[i][k] - y[j][k]|
+ *               TTTS_DTW_L2: c[i][j] = sqrtf(sum_k (x[i][k] - y[j][k])^2)
+ *               the sum runs over k = 0 .. C-1 in that order, whatever B, the padding or the strides
+ *   recurrence  D[0][0] = c[0][0],  D[i][j] = c[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]),  a predecessor that does not exist
+ *               counting as +inf
+ *   tie rule    the FIRST minimum wins in the order diagonal (i-1, j-1), then (i-1, j), then (i, j-1)
+ *   cost        (B,) fp32: D[n_b-1][m_b-1]
+ *   path_len    (B,) int64: cells on the path backtracked from (n_b-1, m_b-1) to (0, 0) by the tie rule
+ *   distance    (B,) fp32: cost / (path_len * C) for L1, cost / path_len for L2
+ *   valid       (B,) uint8: n_b > 0 && m_b > 0; an invalid row has cost, distance and path_len 0 and an all -1 path row
+ *   path        NULL, or (B, Tx + Ty - 1, 2) int32: the cells (i, j) in order from (0, 0), -1 behind path_len
+ * ws: 4-byte aligned, ttts_dtw_workspace_bytes(B, Tx, Ty) bytes =
+ *   B * 4 * (Tx * Ty + S * (Tx + 63) * 64 + S * Tx + 2 * (Tx + Ty)),  K = the least of 1, 2, 4, 8, 16 with 64 * K >= Ty (16 beyond),
+ *   S = ceil(Ty / (64 * K))
+ * -- the staged cell costs, one 32-bit word of 2-bit directions per lane and step (2 bits a cell once Ty >= 1024), the last
+ * column of each strip of 64 * K columns, and the path in backtrack order; 0 for a size that is not positive or above 4096.  A
+ * caller with many utterances runs them in groups to bound it (transformertts_amd.metrics.dtw_distance does).
+ * Refused before any launch, naming the value: null pointers (path may be NULL), non-positive sizes, a row stride < C, negative
+ * batch strides, an unknown metric, Tx or Ty > 4096, B > 65535 (the grid), a workspace that is misaligned or too small. */
+#define TTTS_DTW_L1 0
+#define TTTS_DTW_L2 1
+size_t ttts_dtw_workspace_bytes(int B, int Tx, int Ty);
+int ttts_dtw(const float* x, int64_t ldx_row, int64_t ldx_batch, const int64_t* x_lens, const float* y, int64_t ldy_row,
+             int64_t ldy_batch, const int64_t* y_lens, int B, int Tx, int Ty, int C, int metric, void* ws, size_t ws_bytes, float* cost,
+             int64_t* path_len, float* distance, uint8_t* valid, int32_t* path, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -5,7 +5,8 @@ Drop-in for the reference's `model` package surface:
 Host code is Python on PyTorch-ROCm (memory, streams, autograd graph, torch.distributed); every
 arithmetic step of the path runs in hand-written HIP kernels behind the C ABI of include/ttts_hip.h.
 """
-__all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionWindow"]
+__all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionWindow", "dtw_distance", "mel_cepstra",
+           "evaluate_synthesis"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -15,4 +16,7 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
     if name == "AttentionWindow":   # the window of Synthesizer.synthesize(window=...)
         from . import synthesis
         return synthesis.AttentionWindow
+    if name in ("dtw_distance", "mel_cepstra", "evaluate_synthesis"):   # free-running validation (metrics.py)
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

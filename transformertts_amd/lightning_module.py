@@ -54,6 +54,12 @@ class LightningModule(_Base):
         if ga is not None:
             self.guided_weight = float(ga['weight'])
             self.guided = GuidedAttentionLoss(sigma=ga.get('sigma', 0.4), heads=ga.get('heads'), layers=ga.get('layers'))
+        # config['training']['free_running_validation'] = {utterances, max_len?, stop_threshold?, metric?, window?: {guide, back,
+        # ahead, layers?, heads?}} (an extension): at the end of a validation epoch the first `utterances` rows of the example
+        # batch are synthesised free-running and scored against their recordings by DTW (metrics.evaluate_synthesis).  Absent or
+        # None: validation logs val_loss alone, as the reference does.
+        self.free_running = config['training'].get('free_running_validation')
+        self._synthesizer = None
         # dropout / scheduled-sampling draws follow torch's process seed folded with the data-parallel rank (the reference
         # draws them from torch's global generator; replicas there differ because their generators advance differently).
         # Derived at the first training_step, not here: Lightning constructs the module before torch.distributed exists.
@@ -122,6 +128,33 @@ class LightningModule(_Base):
         if self.valid_losses:
             self.log('val_loss', sum(self.valid_losses) / len(self.valid_losses), on_epoch=True)
         self.valid_losses.clear()
+        if self.free_running is not None and self.example_batch is not None:
+            self._free_running_validation()
+
+    def _free_running_validation(self):
+        """val_free_mel_dtw / val_free_len_ratio / val_free_unfinished: means over the valid rows of the first `utterances`
+        utterances of the example batch, synthesised by a Synthesizer kept on the module (built here, when the model is on its
+        device; a model it refuses raises its ValueError).  One host read, for the three floats."""
+        from .metrics import evaluate_synthesis
+        from .synthesis import AttentionWindow, Synthesizer
+        fr = self.free_running
+        if self._synthesizer is None:
+            self._synthesizer = Synthesizer(self.model)
+        n = int(fr['utterances'])
+        phoneme, melspec, phoneme_lens, melspec_lens = (t[:n] for t in prepare_batch(self.example_batch, self.device))
+        window = AttentionWindow(**fr['window']) if fr.get('window') is not None else None
+        was_training = [(mod, mod.training) for mod in self.model.modules()]      # (the synthesizer puts the model in eval mode)
+        try:
+            res = evaluate_synthesis(self._synthesizer, phoneme, phoneme_lens, melspec, melspec_lens, max_len=fr.get('max_len', 1500),
+                                     stop_threshold=fr.get('stop_threshold', 0.5), window=window, metric=fr.get('metric', 'l1'))
+        finally:
+            for mod, flag in was_training:
+                mod.training = flag
+        valid = res['valid'].to(torch.float32)
+        rows = torch.stack([res['distance'], res['len_ratio'], res['unfinished'].to(torch.float32)])
+        means = ((rows * valid).sum(1) / valid.sum().clamp(min=1.0)).tolist()
+        for name, v in zip(('val_free_mel_dtw', 'val_free_len_ratio', 'val_free_unfinished'), means):
+            self.log(name, v, on_epoch=True)
 
     def configure_optimizers(self):
         # same Adam arithmetic as the reference (lightning_module.py:160-163), fused over flat buffers; `fused_clip_norm`
