@@ -593,6 +593,44 @@ size_t ttts_dtw_workspace_bytes(int B, int Tx, int Ty);
 int ttts_dtw(const float* x, int64_t ldx_row, int64_t ldx_batch, const int64_t* x_lens, const float* y, int64_t ldy_row,
              int64_t ldy_batch, const int64_t* y_lens, int B, int Tx, int Ty, int C, int metric, void* ws, size_t ws_bytes, float* cost,
              int64_t* path_len, float* distance, uint8_t* valid, int32_t* path, void* stream);
+/* ---- log-mel front end: a ragged batch of waveforms to model-ready mel batches (ABI v23; audio.hip, fft_lds.h): what
+ * librosa.stft(center=True, pad_mode='reflect', window='hann') -> abs -> librosa.filters.mel(norm='slaney') -> log(clip) computes,
+ * in one launch, with no padded copy of the signal and no spectrogram in HBM.
+ *   wave        (B, Nmax) fp32, utterance b at wave + b * ld_batch; len_b = wave_lens[b] (int64, device) clamped to [0, Nmax].
+ *               Samples at or beyond len_b are never read.
+ *   framing     frame t covers samples g = t * hop - n_fft/2 + n, n = 0 .. n_fft - 1
+ *   reflection  g < 0 reads sample -g; g >= len reads sample 2 * (len - 1) - g (the edge sample is not repeated)
+ *   frames      frames = 1 + len / hop, written to mel_lens[b] (int64); Tmax = 1 + Nmax / hop rows per utterance in `out`.
+ *               len <= n_fft/2 cannot be reflected: mel_lens[b] = 0 and zero rows, nothing of the utterance is read
+ *   window      periodic Hann, 0.5 - 0.5 cos(2 pi n / win_length), zero-padded to n_fft, left pad (n_fft - win_length) / 2
+ *   transform   X[k] = sum_n w[n] x[n] exp(-2 pi i k n / n_fft), k = 0 .. n_fft/2, fp32, in LDS; n_fft in {256, 512, 1024, 2048}
+ *   mel         filter f = sum_i weights[offset_f + i] * |X[first_f + i]|, i = 0 .. count_f - 1 in this order
+ *   value       TTTS_AUDIO_LOGMEL: log(max(mel, clip_val)) -- a mel <= clip_val gives exactly (float)log((double)clip_val) --
+ *               then, mean_std != NULL, (x - mean) / (std + 1e-8) with mean = mean_std[0], std = mean_std[1] read on the device;
+ *               out is (B, Tmax, n_mels).  TTTS_AUDIO_MAGNITUDE: |X[k]|, out is (B, Tmax, n_fft/2 + 1), mean_std is not read.
+ *               Rows at or beyond mel_lens[b] are written as zeros in both modes.
+ * `tables` is one device buffer of 4-byte words that the caller fills (transformertts_amd.audio builds it in fp64 and rounds):
+ *   8 header words (0x4C454D54, n_fft, win_length, n_mels, nnz, 0, 0, 0) | window (n_fft floats) | cos, -sin of 2 pi k / (n_fft/2),
+ *   k < n_fft/2 (n_fft/2 floats each) | cos, -sin of 2 pi k / n_fft, k <= n_fft/4 (n_fft/4 + 1 floats each) | first_f, count_f,
+ *   offset_f (n_mels int32 each) | weights (nnz floats).  ttts_audio_tables_bytes gives its size (0 for an n_fft outside the set
+ *   or a size < 1); ttts_audio_tables_check reads a HOST copy before it is uploaded and refuses an n_fft outside the set,
+ *   win_length > n_fft or < 1, a size or header that does not match, a filter that leaves the n_fft/2 + 1 bins, offsets that
+ *   are not the running sum of the counts.  The kernel clamps what it reads from the table, so no table makes it load out of bounds.
+ * ttts_logmel_stats: sums[b] = (sum x, sum x^2) in double over the rows < mel_lens[b] (clamped to [0, Tmax]) of mel
+ *   (B, Tmax, n_mels) contiguous, one workgroup per utterance, a fixed order, no atomics: two calls agree bit for bit.  The data
+ *   set's mean = S / count, std = sqrt(Q / count - mean^2 + 1e-8) over the utterances' sums (preprocess.py:45-72).
+ * No host read, no allocation, capturable into a HIP graph.  Refused before any launch, naming the value: null pointers
+ * (mean_std may be NULL), B < 1 or a size < 1, n_fft not in the supported set, hop < 1 or hop > n_fft, an unknown mode, a batch
+ * stride < Nmax, Nmax > 2^30, n_mels > 512 or nnz > 4096 (the filters are staged in LDS), clip_val <= 0, misaligned pointers (4 bytes;
+ * 8 for wave_lens, mel_lens and sums), B > 65535 (the grid). */
+#define TTTS_AUDIO_LOGMEL 0
+#define TTTS_AUDIO_MAGNITUDE 1
+size_t ttts_audio_tables_bytes(int n_fft, int n_mels, int nnz);
+int ttts_audio_tables_check(const void* host_tables, size_t bytes, int n_fft, int win_length, int n_mels, int nnz);
+int ttts_logmel(const float* wave, int64_t ld_batch, const int64_t* wave_lens, int B, int Nmax, int n_fft, int hop, int n_mels,
+                int nnz, const void* tables, float clip_val, const float* mean_std, float* out, int64_t* mel_lens, int mode,
+                void* stream);
+int ttts_logmel_stats(const float* mel, const int64_t* mel_lens, int B, int Tmax, int n_mels, double* sums, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -6,7 +6,7 @@ Host code is Python on PyTorch-ROCm (memory, streams, autograd graph, torch.dist
 arithmetic step of the path runs in hand-written HIP kernels behind the C ABI of include/ttts_hip.h.
 """
 __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionWindow", "dtw_distance", "mel_cepstra",
-           "evaluate_synthesis"]
+           "evaluate_synthesis", "MelFrontEnd", "mel_filterbank", "read_wav", "normalize", "denormalize"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -19,4 +19,7 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
     if name in ("dtw_distance", "mel_cepstra", "evaluate_synthesis"):   # free-running validation (metrics.py)
         from . import metrics
         return getattr(metrics, name)
+    if name in ("MelFrontEnd", "mel_filterbank", "read_wav", "normalize", "denormalize"):   # log-mel front end (audio.py)
+        from . import audio
+        return getattr(audio, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -99,6 +99,10 @@ SIGNATURES = {
     "ttts_alignment_mas": (I, [P, I, L, L, L, P, P, P, I, I, I, I, P, Z, P, P, P]),
     "ttts_dtw_workspace_bytes": (Z, [I, I, I]),
     "ttts_dtw": (I, [P, L, L, P, P, L, L, P, I, I, I, I, I, P, Z, P, P, P, P, P, P]),
+    "ttts_audio_tables_bytes": (Z, [I, I, I]),
+    "ttts_audio_tables_check": (I, [P, Z, I, I, I, I]),
+    "ttts_logmel": (I, [P, L, P, I, I, I, I, I, I, P, F, P, P, P, I, P]),
+    "ttts_logmel_stats": (I, [P, P, I, I, I, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

@@ -1,0 +1,323 @@
+"""Log-mel front end (csrc/audio.hip, C ABI v23): waveform -> the model-ready mel batch, the counterpart of the reference's
+`audio.py:15-51,70-75` without librosa.
+
+    fe = MelFrontEnd(config['audio'], device='cuda')          # tables built once (fp64 -> fp32) and uploaded
+    out = fe(wave, wave_lens)                                  # {'melspec': (B, Tmax, n_mels) fp32, 'melspec_lens': (B,) int64}
+    mag = fe.spectrogram(wave, wave_lens)                      # {'spectrogram': (B, Tmax, n_fft/2+1), 'melspec_lens'}
+    s, q, n = fe.stats(out['melspec'], out['melspec_lens'])    # device scalars: sum, sum of squares (fp64), count (int64)
+    fe.set_stats(mean, std)                                    # floats or device scalars; later calls normalise
+
+`wave` is (B, Nmax) fp32 on the device, `wave_lens` (B,) integers; samples at or beyond a length are never read.  What is
+computed is librosa.stft(center=True, pad_mode='reflect', window='hann') -> abs -> librosa.filters.mel(norm='slaney') ->
+log(max(., clip_val)) [-> (x - mean) / (std + 1e-8)], restated from the documented definitions: frame t covers samples
+t * hop - n_fft/2 ... + n_fft - 1, indices outside [0, len) reflected without repeating the edge, frames = 1 + len // hop,
+Tmax = 1 + Nmax // hop, rows at or beyond a row's frames are zeros.  Nothing is read back: a call captures into a HIP graph.
+"""
+from __future__ import annotations
+
+import math
+import struct
+import wave as _wave
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+
+N_FFT = (256, 512, 1024, 2048)                  # audio.hip audio_n_fft_ok
+MODES = {"logmel": 0, "magnitude": 1}           # TTTS_AUDIO_LOGMEL / TTTS_AUDIO_MAGNITUDE
+MAGIC = 0x4C454D54
+HEADER = 8
+
+
+def hz_to_mel(f):
+    """the Slaney scale: linear (200/3 Hz per mel) below 1 kHz, logarithmic (27 mels per factor 6.4) above"""
+    f = np.asarray(f, dtype=np.float64)
+    lin = f / (200.0 / 3.0)
+    log = 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (math.log(6.4) / 27.0)
+    return np.where(f >= 1000.0, log, lin)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((math.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_filterbank(sample_rate: float, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None) -> np.ndarray:
+    """(n_mels, n_fft/2+1) float64: librosa.filters.mel(htk=False, norm='slaney') from its definition.  n_mels + 2 points equally
+    spaced in mel between fmin and fmax; weight of bin frequency f in filter i = max(0, min((f - f_i) / (f_{i+1} - f_i),
+    (f_{i+2} - f) / (f_{i+2} - f_{i+1}))) * 2 / (f_{i+2} - f_i)."""
+    fmax = sample_rate / 2.0 if fmax is None else float(fmax)
+    if n_fft < 2 or n_mels < 1 or not 0.0 <= fmin < fmax:
+        raise ValueError(f"mel_filterbank: need n_fft >= 2, n_mels >= 1 and 0 <= fmin < fmax (n_fft {n_fft}, n_mels {n_mels}, "
+                         f"fmin {fmin}, fmax {fmax})")
+    bins = np.linspace(0.0, sample_rate / 2.0, n_fft // 2 + 1)
+    edges = mel_to_hz(np.linspace(float(hz_to_mel(fmin)), float(hz_to_mel(fmax)), n_mels + 2))
+    width = np.diff(edges)
+    ramps = edges[:, None] - bins[None, :]
+    lower = -ramps[:-2] / width[:-1, None]
+    upper = ramps[2:] / width[1:, None]
+    return np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (edges[2:] - edges[:-2]))[:, None]
+
+
+def hann_window(win_length: int, n_fft: int) -> np.ndarray:
+    """periodic Hann of win_length, zero-padded to n_fft, left pad (n_fft - win_length) // 2; float64"""
+    if not 1 <= win_length <= n_fft:
+        raise ValueError(f"win_length must be in [1, n_fft] (win_length {win_length}, n_fft {n_fft})")
+    w = np.zeros(n_fft, dtype=np.float64)
+    left = (n_fft - win_length) // 2
+    w[left:left + win_length] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length) / win_length)
+    return w
+
+
+def pack_filters(fb: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """dense (n_mels, bins) -> (first, count, offset int32 arrays, weights fp32): per row the span from its first to its last
+    non-zero weight (an all-zero row: count 0)"""
+    first, count, weights = [], [], []
+    for row in fb:
+        nz = np.flatnonzero(row)
+        a, n = (int(nz[0]), int(nz[-1]) - int(nz[0]) + 1) if nz.size else (0, 0)
+        first.append(a)
+        count.append(n)
+        weights.append(row[a:a + n])
+    count = np.asarray(count, dtype=np.int32)
+    offset = (np.cumsum(count) - count).astype(np.int32)
+    return np.asarray(first, dtype=np.int32), count, offset, np.concatenate(weights).astype(np.float32)
+
+
+def unpack_filters(first, count, offset, weights, bins: int) -> np.ndarray:
+    fb = np.zeros((len(first), bins), dtype=np.float32)
+    for f, (a, n, o) in enumerate(zip(first, count, offset)):
+        fb[f, a:a + n] = weights[o:o + n]
+    return fb
+
+
+def table_layout(n_fft: int, n_mels: int, nnz: int) -> Dict[str, int]:
+    """word offsets of the sections of the table buffer (audio.hip audio_tables)"""
+    M = n_fft // 2
+    lay, at = {}, HEADER
+    for name, n in (("window", n_fft), ("tw_re", M), ("tw_im", M), ("pw_re", M // 2 + 1), ("pw_im", M // 2 + 1), ("first", n_mels),
+                    ("count", n_mels), ("offset", n_mels), ("weights", nnz)):
+        lay[name] = at
+        at += n
+    lay["words"] = at
+    return lay
+
+
+def build_tables(n_fft: int, win_length: int, fb: np.ndarray) -> Tuple[np.ndarray, int]:
+    """the kernel's table buffer as int32 words (every value built in float64 and rounded to fp32 once) and its nnz"""
+    if n_fft not in N_FFT:
+        raise ValueError(f"n_fft must be one of {N_FFT}, got {n_fft}")
+    M = n_fft // 2
+    if fb.shape[1] != M + 1:
+        raise ValueError(f"the filter bank must have n_fft/2+1 = {M + 1} columns, got {fb.shape}")
+    first, count, offset, weights = pack_filters(fb)
+    nnz = int(weights.size)
+    if nnz < 1:
+        raise ValueError("the filter bank is empty")
+    lay = table_layout(n_fft, fb.shape[0], nnz)
+    buf = np.zeros(lay["words"], dtype=np.int32)
+    buf[:5] = np.asarray([MAGIC, n_fft, win_length, fb.shape[0], nnz], dtype=np.int64).astype(np.int32)
+    f32 = buf.view(np.float32)
+    k = np.arange(M, dtype=np.float64)
+    f32[lay["window"]:lay["window"] + n_fft] = hann_window(win_length, n_fft)
+    f32[lay["tw_re"]:lay["tw_re"] + M] = np.cos(2.0 * np.pi * k / M)
+    f32[lay["tw_im"]:lay["tw_im"] + M] = -np.sin(2.0 * np.pi * k / M)
+    k = np.arange(M // 2 + 1, dtype=np.float64)
+    f32[lay["pw_re"]:lay["pw_re"] + M // 2 + 1] = np.cos(2.0 * np.pi * k / n_fft)
+    f32[lay["pw_im"]:lay["pw_im"] + M // 2 + 1] = -np.sin(2.0 * np.pi * k / n_fft)
+    for name, arr in (("first", first), ("count", count), ("offset", offset)):
+        buf[lay[name]:lay[name] + arr.size] = arr
+    f32[lay["weights"]:lay["weights"] + nnz] = weights
+    return buf, nnz
+
+
+def normalize(mel, mean, std):
+    return (mel - mean) / (std + 1e-8)
+
+
+def denormalize(mel, mean, std):
+    return (mel * (std + 1e-8)) + mean
+
+
+def read_wav(path: str, sample_rate: int) -> np.ndarray:
+    """mono RIFF PCM16 / PCM24 / PCM32 / IEEE float32 -> float32 in [-1, 1); raises if the file's rate is not `sample_rate`
+    (there is no resampler) or it is not mono.  Standard library only."""
+    with open(path, "rb") as fh:
+        head = fh.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise ValueError(f"read_wav: {path} is not a RIFF/WAVE file")
+        fmt = data = None
+        while True:
+            ck = fh.read(8)
+            if len(ck) < 8:
+                break
+            tag, size = ck[:4], struct.unpack("<I", ck[4:])[0]
+            if tag == b"fmt ":
+                fmt = fh.read(size)
+            elif tag == b"data":
+                data = fh.read(size)
+            else:
+                fh.seek(size, 1)
+            if size & 1:
+                fh.seek(1, 1)
+            if fmt is not None and data is not None:
+                break
+    if fmt is None or data is None or len(fmt) < 16:
+        raise ValueError(f"read_wav: {path} has no fmt or data chunk")
+    code, channels, rate, _, _, bits = struct.unpack("<HHIIHH", fmt[:16])
+    if code == 0xFFFE and len(fmt) >= 26:        # WAVE_FORMAT_EXTENSIBLE: the sub-format's first two bytes
+        code = struct.unpack("<H", fmt[24:26])[0]
+    if channels != 1:
+        raise ValueError(f"read_wav: {path} has {channels} channels, mono expected")
+    if rate != int(sample_rate):
+        raise ValueError(f"read_wav: {path} is sampled at {rate} Hz, {int(sample_rate)} Hz expected (there is no resampler)")
+    if code == 1 and bits == 16:
+        return (np.frombuffer(data[:len(data) // 2 * 2], dtype="<i2").astype(np.float32) / np.float32(32768.0))
+    if code == 1 and bits == 24:
+        raw = np.frombuffer(data[:len(data) // 3 * 3], dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = raw[:, 0] | (raw[:, 1] << 8) | (raw[:, 2] << 16)
+        v = np.where(v >= 1 << 23, v - (1 << 24), v)
+        return (v.astype(np.float64) / float(1 << 23)).astype(np.float32)
+    if code == 1 and bits == 32:
+        return (np.frombuffer(data[:len(data) // 4 * 4], dtype="<i4").astype(np.float64) / float(1 << 31)).astype(np.float32)
+    if code == 3 and bits == 32:
+        return np.frombuffer(data[:len(data) // 4 * 4], dtype="<f4").astype(np.float32)
+    raise ValueError(f"read_wav: {path}: format code {code} with {bits} bits is not PCM16/24/32 or float32")
+
+
+def write_wav_pcm16(path: str, samples: np.ndarray, sample_rate: int) -> None:
+    """mono PCM16 through the standard library's `wave` (tests and examples)"""
+    pcm = np.clip(np.round(np.asarray(samples, dtype=np.float64) * 32768.0), -32768, 32767).astype("<i2")
+    with _wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(sample_rate))
+        w.writeframes(pcm.tobytes())
+
+
+class MelFrontEnd:
+    """Tables for one audio config, built once; every call is one kernel launch (two for `stats`)."""
+
+    def __init__(self, audio_config: Dict, device=None, mean=None, std=None, clip_val: float = 1e-5):
+        import torch
+        from . import _lib
+        c = audio_config
+        self.sample_rate = int(c["sample_rate"])
+        self.n_fft, self.hop = int(c["n_fft"]), int(c["hop_length"])
+        self.win_length = int(c.get("win_length") or self.n_fft)
+        self.n_mels = int(c["n_mels"])
+        self.fmin = float(c.get("fmin", 0.0))
+        self.fmax = float(c["fmax"]) if c.get("fmax") is not None else self.sample_rate / 2.0
+        self.clip_val = float(clip_val)
+        if self.n_fft not in N_FFT:
+            raise ValueError(f"MelFrontEnd: n_fft must be one of {N_FFT}, got {self.n_fft}")
+        if not 1 <= self.hop <= self.n_fft:
+            raise ValueError(f"MelFrontEnd: hop_length must be in [1, n_fft] (hop_length {self.hop}, n_fft {self.n_fft})")
+        if not 1 <= self.win_length <= self.n_fft:
+            raise ValueError(f"MelFrontEnd: win_length must be in [1, n_fft] (win_length {self.win_length}, n_fft {self.n_fft})")
+        self.filterbank = mel_filterbank(self.sample_rate, self.n_fft, self.n_mels, self.fmin, self.fmax)
+        self.tables_host, self.nnz = build_tables(self.n_fft, self.win_length, self.filterbank)
+        lib = _lib.load()
+        nbytes = self.tables_host.nbytes
+        if lib.ttts_audio_tables_bytes(self.n_fft, self.n_mels, self.nnz) != nbytes:
+            raise RuntimeError("MelFrontEnd: the table layout disagrees with the library")
+        _lib.check(lib.ttts_audio_tables_check(self.tables_host.ctypes.data, nbytes, self.n_fft, self.win_length, self.n_mels, self.nnz),
+                   "ttts_audio_tables_check")
+        if not torch.cuda.is_available():
+            raise RuntimeError("MelFrontEnd needs the HIP device (no CPU fallback)")
+        self.device = torch.device(device if device is not None else "cuda")
+        self.tables = torch.from_numpy(self.tables_host).to(self.device)
+        self.mean_std = None
+        if (mean is None) != (std is None):
+            raise ValueError("MelFrontEnd: give both `mean` and `std`, or neither")
+        if mean is not None:
+            self.set_stats(mean, std)
+
+    # ------------------------------------------------------------------ statistics
+    def set_stats(self, mean, std) -> None:
+        """normalise from now on with (x - mean) / (std + 1e-8); floats, or device scalars (then nothing is read back).  The two
+        values live in one device buffer that is overwritten in place, so a captured call follows them.  None, None: stop."""
+        import torch
+        if mean is None and std is None:
+            self.mean_std = None
+            return
+        if self.mean_std is None:
+            self.mean_std = torch.empty(2, dtype=torch.float32, device=self.device)
+        for i, v in enumerate((mean, std)):
+            if isinstance(v, torch.Tensor):
+                self.mean_std[i].copy_(v.reshape(()).to(torch.float32))
+            else:
+                self.mean_std[i] = float(v)
+
+    def stats(self, melspec, melspec_lens):
+        """-> (sum, sum of squares, count) of the valid rows of an UNNORMALISED log-mel batch: fp64, fp64, int64 device scalars.
+        Per utterance in a fixed order on the device (ttts_logmel_stats), utterances added in fp64."""
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        self._chk(melspec, "stats.melspec", torch.float32)
+        if melspec.dim() != 3 or melspec.size(2) != self.n_mels or min(melspec.shape) < 1:
+            raise ValueError(f"stats: melspec must be (B, T, {self.n_mels}), got {tuple(melspec.shape)}")
+        B, T, _ = melspec.shape
+        lens = self._lens(melspec_lens, B, "stats.melspec_lens")
+        mel = melspec.detach().contiguous()
+        sums = torch.empty(B, 2, dtype=torch.float64, device=mel.device)
+        _lib.check(_lib.load().ttts_logmel_stats(_p(mel), _p(lens), B, T, self.n_mels, _p(sums), _stream()), "ttts_logmel_stats")
+        total = sums.sum(0)
+        return total[0], total[1], lens.clamp(0, T).sum() * self.n_mels
+
+    @staticmethod
+    def mean_std_from(total, total_sq, count):
+        """preprocess.py:59-61: mean = S / n, std = sqrt(Q / n - mean^2 + 1e-8); works on floats and on device scalars"""
+        mean = total / count
+        var = total_sq / count - mean ** 2
+        return mean, (var + 1e-8) ** 0.5
+
+    # ------------------------------------------------------------------ the two calls
+    def _chk(self, t, name, dtype):
+        if not t.is_cuda:
+            raise ValueError(f"MelFrontEnd.{name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback), got {t.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"MelFrontEnd.{name}: expected dtype {dtype}, got {t.dtype}")
+
+    def _lens(self, lens, B, name):
+        import torch
+        if tuple(lens.shape) != (B,):
+            raise ValueError(f"MelFrontEnd.{name} must have shape ({B},), got {tuple(lens.shape)}")
+        if lens.dtype.is_floating_point or lens.dtype == torch.bool:
+            raise ValueError(f"MelFrontEnd.{name} must be integers, got {lens.dtype}")
+        if not lens.is_cuda:                       # host lengths: the one place the unreflectable length can be refused
+            if lens.numel() and int(lens.min()) <= self.n_fft // 2 and "wave" in name:
+                raise ValueError(f"MelFrontEnd.{name}: an utterance of {int(lens.min())} samples cannot be reflected "
+                                 f"(n_fft/2 + 1 = {self.n_fft // 2 + 1} at the least)")
+            lens = lens.to(self.device)
+        return lens.to(torch.int64).contiguous()
+
+    def _run(self, wave, wave_lens, mode: str):
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        if wave.dim() != 2 or min(wave.shape) < 1:
+            raise ValueError(f"MelFrontEnd: wave must be (B, Nmax), got {tuple(wave.shape)}")
+        self._chk(wave, "wave", torch.float32)
+        B, Nmax = wave.shape
+        lens = self._lens(wave_lens, B, "wave_lens")
+        wave = wave.detach()
+        if (Nmax > 1 and wave.stride(1) != 1) or (B > 1 and wave.stride(0) < Nmax):
+            wave = wave.contiguous()
+        ld = wave.stride(0) if B > 1 else Nmax
+        Tmax = 1 + Nmax // self.hop
+        width = self.n_mels if mode == "logmel" else self.n_fft // 2 + 1
+        out = torch.empty(B, Tmax, width, dtype=torch.float32, device=wave.device)
+        mel_lens = torch.empty(B, dtype=torch.int64, device=wave.device)
+        _lib.check(_lib.load().ttts_logmel(_p(wave), ld, _p(lens), B, Nmax, self.n_fft, self.hop, self.n_mels, self.nnz, _p(self.tables),
+                                           self.clip_val, _p(self.mean_std), _p(out), _p(mel_lens), MODES[mode], _stream()),
+                   "ttts_logmel")
+        return out, mel_lens
+
+    def __call__(self, wave, wave_lens):
+        mel, lens = self._run(wave, wave_lens, "logmel")
+        return {"melspec": mel, "melspec_lens": lens}
+
+    def spectrogram(self, wave, wave_lens):
+        mag, lens = self._run(wave, wave_lens, "magnitude")
+        return {"spectrogram": mag, "melspec_lens": lens}
