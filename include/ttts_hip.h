@@ -631,6 +631,49 @@ int ttts_logmel(const float* wave, int64_t ld_batch, const int64_t* wave_lens, i
                 int nnz, const void* tables, float clip_val, const float* mean_std, float* out, int64_t* mel_lens, int mode,
                 void* stream);
 int ttts_logmel_stats(const float* mel, const int64_t* mel_lens, int B, int Tmax, int n_mels, double* sums, void* stream);
+/* ---- Griffin-Lim vocoder: a ragged batch of (normalised) log-mels back to waveforms (ABI v24; vocoder.hip, audio_common.h,
+ * fft_lds.h): librosa.feature.inverse.mel_to_audio's fast Griffin-Lim with a pseudo-inverse mel basis, restated from the
+ * documented definitions on the front end's tables and conventions.  bins = n_fft/2 + 1.
+ *   magnitude   ttts_mel_to_magnitude: x = mel[b, t, :] (row t of utterance b at mel + b * ld_batch + t * ld_row, n_mels floats);
+ *               mean_std != NULL: x * (std + 1e-8) + mean, read on the device from the front end's two floats; m[f] = expf(x[f]);
+ *               mag[k] = max(sum_f pinv[k, f] * m[f], floor), f ascending; pinv is (bins, n_mels) fp32 row-major (the caller forms
+ *               numpy.linalg.pinv of the mel basis in fp64 and rounds once).  frames_b = melspec_lens[b] clamped to [0, Tmax].  A
+ *               row is vocodable iff (frames_b - 1) * hop > n_fft/2 -- anything shorter the front end could not reflect -- and
+ *               keeps its frames; otherwise its effective frames are 0.  The effective frames are written to `frames` (int64);
+ *               the two transforms read that array, never melspec_lens.  mag is (B, Tmax, bins); rows at or beyond the effective
+ *               frames are zeros, nothing at or beyond a length is read.
+ *   inverse     ttts_istft: spec is (B, Tmax, bins, 2) fp32 (re, im); x_t = irfft(spec[b, t], n_fft), the imaginary parts of bin 0
+ *               and bin n_fft/2 ignored, the 1/n_fft applied here; with g' = t * hop + n over the frames t < frames_b in ascending
+ *               t: y[g'] = sum_t w[n] x_t[n], env[g'] = sum_t w[n]^2; wave[b, g] = env > 1.17549435e-38f ? y / env : y at
+ *               g' = g + n_fft/2 for g < wave_lens[b] = frames_b > 0 ? (frames_b - 1) * hop : 0 (written, int64); samples from
+ *               there to Nmax = (Tmax - 1) * hop are zeros; wave is (B, Nmax).  Any frames_b >= 1 is taken (clamped to [0, Tmax]).
+ *               A gather: a workgroup owns 2 * n_fft consecutive samples and adds the frames that touch them in ascending t, so a
+ *               sample's bits do not depend on the grid, the batch or the call.
+ *   forward     ttts_stft_project: reb = STFT(wave) exactly as ttts_logmel frames, reflects, windows and transforms; wave is
+ *               (B, Nmax) at stride ld_batch, Tmax = 1 + Nmax / hop.  Give wave_lens (then frames = 1 + len / hop by the front
+ *               end's rule, 0 for len <= n_fft/2) or frames (then len = (frames - 1) * hop, and frames whose len <= n_fft/2 count
+ *               as 0): one of them.  frames_out != NULL receives the frames used.  mag == NULL: spec = reb, rows beyond the frames
+ *               zeros -- the complex STFT.  mag given ((B, Tmax, bins)): t = reb - (momentum / (1 + momentum)) * prev;
+ *               prev <- reb in place ((B, Tmax, bins, 2)); a2 = |t|^2; spec = mag * (a2 > 1e-30f ? t * rsqrt(a2) : (1, 0)); rows
+ *               beyond the frames are not touched.  momentum in [0, 1); momentum = 0 needs no prev.
+ *   Griffin-Lim spec = mag * init (unit phases); prev = 0; n_iter times { wave = istft(spec); project }; wave = istft(spec):
+ *               n_iter + 1 inverse and n_iter forward launches (transformertts_amd.audio.Vocoder).
+ * `tables` is the front end's table buffer (window, roots, w^k; the filter sections are not read).  ttts_vocoder_pinv_check reads a
+ * HOST copy of pinv before it is uploaded: the size and finite values.  No host read, no allocation, no atomics, the same bits
+ * on every call, capturable into a HIP graph.  Refused before any launch, with a message: null pointers (mean_std, mag, prev,
+ * frames_out and one of wave_lens / frames may be NULL), B < 1 or a size < 1, n_fft not in {256, 512, 1024, 2048}, hop < 1 or
+ * hop > n_fft, Tmax < 2, more than 2^30 samples, n_mels > 512, strides that do not cover a row, floor <= 0, momentum outside
+ * [0, 1), momentum > 0 without prev, prev or momentum without mag, misaligned pointers (4 bytes; 8 for spec, prev and the int64
+ * arrays), B > 65535 (the grid). */
+int ttts_vocoder_pinv_check(const void* host_pinv, size_t bytes, int n_fft, int n_mels);
+int ttts_mel_to_magnitude(const float* mel, int64_t ld_row, int64_t ld_batch, const int64_t* melspec_lens, int B, int Tmax, int n_fft,
+                          int hop, int n_mels, const float* pinv, const float* mean_std, float floor, float* mag, int64_t* frames,
+                          void* stream);
+int ttts_istft(const float* spec, const int64_t* frames, int B, int Tmax, int n_fft, int hop, const void* tables, float* wave,
+               int64_t* wave_lens, void* stream);
+int ttts_stft_project(const float* wave, int64_t ld_batch, const int64_t* wave_lens, const int64_t* frames, int B, int Nmax, int n_fft,
+                      int hop, const void* tables, const float* mag, float* prev, float momentum, float* spec, int64_t* frames_out,
+                      void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""A `.npz` written by tools/preprocess_mel.py (or a synthesised mel saved the same way) -> a PCM16 `.wav`, through `Vocoder`
+(csrc/vocoder.hip): pseudo-inverse mel basis, then fast Griffin-Lim.
+
+    python tools/vocode_mel.py --config config.yaml --npz FILE.npz [--stats stats.json] --out FILE.wav [--n-iter 32]
+
+`melspec` in the file is (n_mels, T) fp32.  With `config['audio']['normalize_mel']` the file holds normalised values and
+`--stats` (the `mean` / `std` file of preprocess_mel.py) is needed to undo that.  The wave has (T - 1) * hop_length samples at
+`config['audio']['sample_rate']`; a mel too short to vocode ((T - 1) * hop_length <= n_fft/2) is refused."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from transformertts_amd import audio  # noqa: E402
+
+
+def make_vocoder(audio_config, mean=None, std=None, **kw):
+    return audio.Vocoder(audio_config, mean=mean, std=std, **kw)
+
+
+def run(config, npz_path, out_path, stats_path=None, make_vocoder=make_vocoder, log=print, **kw):
+    a = config["audio"]
+    mean = std = None
+    if a.get("normalize_mel"):
+        if stats_path is None:
+            raise ValueError("config['audio']['normalize_mel'] is set: --stats (the mean / std file of preprocess_mel.py) is needed")
+        with open(stats_path, "r", encoding="utf-8") as f:
+            stats = json.load(f)
+        mean, std = float(stats["mean"]), float(stats["std"])
+    with np.load(npz_path, allow_pickle=True) as d:
+        mel = np.asarray(d["melspec"], dtype=np.float32)
+    n_mels, hop, n_fft = int(a["n_mels"]), int(a["hop_length"]), int(a["n_fft"])
+    if mel.ndim != 2 or mel.shape[0] != n_mels:
+        raise ValueError(f"{npz_path}: melspec must be ({n_mels}, T), got {mel.shape}")
+    T = mel.shape[1]
+    if (T - 1) * hop <= n_fft // 2:
+        raise ValueError(f"{npz_path}: {T} frames are too few to vocode ((T - 1) * hop_length must exceed n_fft/2 = {n_fft // 2})")
+    voc = make_vocoder(a, mean=mean, std=std, **kw)
+    out = voc(torch.from_numpy(np.ascontiguousarray(mel.T))[None].to(voc.device), torch.tensor([T], dtype=torch.int64))
+    n = int(out["wave_lens"][0])
+    wave = out["wave"][0, :n].cpu().numpy()
+    peak = float(np.abs(wave).max()) if n else 0.0
+    if peak >= 1.0:                                                   # PCM16 clips at full scale
+        log(f"peak {peak:.3f}: scaled to 0.99")
+        wave = wave * (0.99 / peak)
+    audio.write_wav_pcm16(out_path, wave, int(a["sample_rate"]))
+    log(f"{n} samples ({n / float(a['sample_rate']):.2f} s) -> {out_path}")
+    return n
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--npz", required=True)
+    ap.add_argument("--stats", default=None)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--n-iter", type=int, default=32)
+    args = ap.parse_args(argv)
+    import yaml
+    with open(args.config, "r") as f:
+        config = yaml.safe_load(f)
+    run(config, args.npz, args.out, stats_path=args.stats, n_iter=args.n_iter)
+
+
+if __name__ == "__main__":
+    main()

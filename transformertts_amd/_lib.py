@@ -103,6 +103,10 @@ SIGNATURES = {
     "ttts_audio_tables_check": (I, [P, Z, I, I, I, I]),
     "ttts_logmel": (I, [P, L, P, I, I, I, I, I, I, P, F, P, P, P, I, P]),
     "ttts_logmel_stats": (I, [P, P, I, I, I, P, P]),
+    "ttts_vocoder_pinv_check": (I, [P, Z, I, I]),
+    "ttts_mel_to_magnitude": (I, [P, L, L, P, I, I, I, I, I, P, P, F, P, P, P]),
+    "ttts_istft": (I, [P, P, I, I, I, I, P, P, P, P]),
+    "ttts_stft_project": (I, [P, L, P, P, I, I, I, I, P, P, P, F, P, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

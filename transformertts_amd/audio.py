@@ -1,5 +1,5 @@
-"""Log-mel front end (csrc/audio.hip, C ABI v23): waveform -> the model-ready mel batch, the counterpart of the reference's
-`audio.py:15-51,70-75` without librosa.
+"""Log-mel front end (csrc/audio.hip, C ABI v23) and Griffin-Lim vocoder (csrc/vocoder.hip, C ABI v24): waveform -> the
+model-ready mel batch and back, the counterpart of the reference's `audio.py:15-51,70-75` without librosa.
 
     fe = MelFrontEnd(config['audio'], device='cuda')          # tables built once (fp64 -> fp32) and uploaded
     out = fe(wave, wave_lens)                                  # {'melspec': (B, Tmax, n_mels) fp32, 'melspec_lens': (B,) int64}
@@ -12,6 +12,17 @@ computed is librosa.stft(center=True, pad_mode='reflect', window='hann') -> abs 
 log(max(., clip_val)) [-> (x - mean) / (std + 1e-8)], restated from the documented definitions: frame t covers samples
 t * hop - n_fft/2 ... + n_fft - 1, indices outside [0, len) reflected without repeating the edge, frames = 1 + len // hop,
 Tmax = 1 + Nmax // hop, rows at or beyond a row's frames are zeros.  Nothing is read back: a call captures into a HIP graph.
+
+    voc = Vocoder(config['audio'], device='cuda', n_iter=32, momentum=0.99)   # owns a MelFrontEnd (voc.front_end) and its tables
+    out = voc(melspec, melspec_lens)                           # {'wave': (B, (Tmax-1)*hop) fp32, 'wave_lens': (B,) int64}
+    voc.magnitude(melspec, melspec_lens)                       # {'spectrogram': (B, Tmax, bins), 'melspec_lens': effective frames}
+    voc.griffin_lim(magnitude, frames)                         # the same dict as voc(...), from linear magnitudes
+    voc.istft(spectrum, frames) / voc.stft(wave, wave_lens)    # the two transforms on their own (complex64 spectra)
+
+The way back is librosa.feature.inverse.mel_to_audio's fast Griffin-Lim, restated: magnitude = max(pinv(mel basis) @ exp(mel),
+floor), then spec = magnitude * init, n_iter times { wave = istft(spec); reb = stft(wave); t = reb - momentum / (1 + momentum) *
+prev; prev = reb; spec = magnitude * t / |t| }, wave = istft(spec).  An utterance is vocodable iff (frames - 1) * hop > n_fft/2
+(the front end can reflect what comes back); its wave has (frames - 1) * hop samples, any other row 0 samples.
 """
 from __future__ import annotations
 
@@ -26,6 +37,8 @@ N_FFT = (256, 512, 1024, 2048)                  # audio.hip audio_n_fft_ok
 MODES = {"logmel": 0, "magnitude": 1}           # TTTS_AUDIO_LOGMEL / TTTS_AUDIO_MAGNITUDE
 MAGIC = 0x4C454D54
 HEADER = 8
+SPAN_MULT = 2                                   # vocoder.hip VOCODER_SPAN_MULT: an inverse-STFT workgroup owns SPAN_MULT * n_fft samples
+MAX_MELS = 512                                  # audio_common.h AUDIO_MAX_MELS
 
 
 def hz_to_mel(f):
@@ -56,6 +69,15 @@ def mel_filterbank(sample_rate: float, n_fft: int, n_mels: int, fmin: float = 0.
     lower = -ramps[:-2] / width[:-1, None]
     upper = ramps[2:] / width[1:, None]
     return np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (edges[2:] - edges[:-2]))[:, None]
+
+
+def inverse_mel_basis(fb: np.ndarray) -> np.ndarray:
+    """(bins, n_mels) float32, C-contiguous: numpy.linalg.pinv of the (n_mels, bins) mel basis, formed in float64 and rounded to
+    fp32 once"""
+    fb = np.asarray(fb, dtype=np.float64)
+    if fb.ndim != 2 or min(fb.shape) < 1:
+        raise ValueError(f"inverse_mel_basis: the mel basis must be (n_mels, bins), got {fb.shape}")
+    return np.ascontiguousarray(np.linalg.pinv(fb).astype(np.float32))
 
 
 def hann_window(win_length: int, n_fft: int) -> np.ndarray:
@@ -321,3 +343,174 @@ class MelFrontEnd:
     def spectrogram(self, wave, wave_lens):
         mag, lens = self._run(wave, wave_lens, "magnitude")
         return {"spectrogram": mag, "melspec_lens": lens}
+
+
+class Vocoder:
+    """Griffin-Lim on the front end's tables; a call is one magnitude launch and 2 n_iter + 1 transform launches, nothing is read
+    back.  With an explicit `init` the whole call captures into a HIP graph (the default init draws from a torch.Generator)."""
+
+    def __init__(self, audio_config: Dict, device=None, mean=None, std=None, n_iter: int = 32, momentum: float = 0.99,
+                 floor: float = 1e-10):
+        import torch
+        from . import _lib
+        self.n_iter, self.momentum, self.floor = int(n_iter), float(momentum), float(floor)
+        if self.n_iter < 0:
+            raise ValueError(f"Vocoder: n_iter must be >= 0, got {n_iter}")
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError(f"Vocoder: momentum must be in [0, 1), got {momentum}")
+        if not self.floor > 0.0:
+            raise ValueError(f"Vocoder: floor must be positive, got {floor}")
+        if int(audio_config["n_mels"]) > MAX_MELS:
+            raise ValueError(f"Vocoder: at most {MAX_MELS} mel filters, got {audio_config['n_mels']}")
+        self.front_end = MelFrontEnd(audio_config, device=device, mean=mean, std=std)
+        fe = self.front_end
+        self.n_fft, self.hop, self.n_mels, self.bins, self.device = fe.n_fft, fe.hop, fe.n_mels, fe.n_fft // 2 + 1, fe.device
+        self.sample_rate = fe.sample_rate
+        self.span = SPAN_MULT * self.n_fft
+        self.pinv_host = inverse_mel_basis(fe.filterbank)
+        _lib.check(_lib.load().ttts_vocoder_pinv_check(self.pinv_host.ctypes.data, self.pinv_host.nbytes, self.n_fft, self.n_mels),
+                   "ttts_vocoder_pinv_check")
+        self.pinv = torch.from_numpy(self.pinv_host).to(self.device)
+
+    def set_stats(self, mean, std) -> None:
+        """the front end's statistics: one buffer, seen by both directions"""
+        self.front_end.set_stats(mean, std)
+
+    @property
+    def mean_std(self):
+        return self.front_end.mean_std
+
+    # ------------------------------------------------------------------ checks
+    def _chk(self, t, name, dtype):
+        if not t.is_cuda:
+            raise ValueError(f"Vocoder.{name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback), got {t.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"Vocoder.{name}: expected dtype {dtype}, got {t.dtype}")
+
+    def _lens(self, lens, B, name):
+        import torch
+        if tuple(lens.shape) != (B,):
+            raise ValueError(f"Vocoder.{name} must have shape ({B},), got {tuple(lens.shape)}")
+        if lens.dtype.is_floating_point or lens.dtype == torch.bool:
+            raise ValueError(f"Vocoder.{name} must be integers, got {lens.dtype}")
+        return lens.to(self.device).to(torch.int64).contiguous()
+
+    def _frames3(self, x, width, what, name):
+        if x.dim() != 3 or x.size(2) != width or min(x.shape) < 1:
+            raise ValueError(f"Vocoder: {name} must be (B, Tmax, {width}) {what}, got {tuple(x.shape)}")
+        if x.size(1) < 2:
+            raise ValueError(f"Vocoder: {name} needs Tmax >= 2 rows, got {tuple(x.shape)}")
+
+    # ------------------------------------------------------------------ the steps
+    def magnitude(self, melspec, melspec_lens):
+        """(normalised) log-mel -> linear magnitudes max(pinv @ exp(mel), floor) and the effective frames (0 for a row that
+        cannot be vocoded)"""
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        self._frames3(melspec, self.n_mels, "log-mels", "melspec")
+        self._chk(melspec, "melspec", torch.float32)
+        B, Tmax, _ = melspec.shape
+        lens = self._lens(melspec_lens, B, "melspec_lens")
+        mel = melspec.detach()
+        if mel.stride(2) != 1 or mel.stride(1) < self.n_mels or (B > 1 and mel.stride(0) < (Tmax - 1) * mel.stride(1) + self.n_mels):
+            mel = mel.contiguous()
+        mag = torch.empty(B, Tmax, self.bins, dtype=torch.float32, device=mel.device)
+        frames = torch.empty(B, dtype=torch.int64, device=mel.device)
+        _lib.check(_lib.load().ttts_mel_to_magnitude(_p(mel), mel.stride(1), mel.stride(0), _p(lens), B, Tmax, self.n_fft, self.hop,
+                                                     self.n_mels, _p(self.pinv), _p(self.mean_std), self.floor, _p(mag), _p(frames),
+                                                     _stream()), "ttts_mel_to_magnitude")
+        return {"spectrogram": mag, "melspec_lens": frames}
+
+    def _istft(self, spec, frames, B, Tmax):
+        """spec: (B, Tmax, bins, 2) fp32 contiguous"""
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        wave = torch.empty(B, (Tmax - 1) * self.hop, dtype=torch.float32, device=spec.device)
+        wave_lens = torch.empty(B, dtype=torch.int64, device=spec.device)
+        _lib.check(_lib.load().ttts_istft(_p(spec), _p(frames), B, Tmax, self.n_fft, self.hop, _p(self.front_end.tables), _p(wave),
+                                          _p(wave_lens), _stream()), "ttts_istft")
+        return wave, wave_lens
+
+    def istft(self, spectrum, frames):
+        """complex64 (B, Tmax, bins) and the rows' frames -> {'wave': (B, (Tmax-1)*hop), 'wave_lens': (frames - 1) * hop};
+        least-squares overlap-add with the front end's window, the n_fft/2 samples of centring removed"""
+        import torch
+        self._frames3(spectrum, self.bins, "complex64", "spectrum")
+        self._chk(spectrum, "spectrum", torch.complex64)
+        B, Tmax, _ = spectrum.shape
+        frames = self._lens(frames, B, "frames")
+        spec = torch.view_as_real(spectrum.detach().contiguous())
+        wave, wave_lens = self._istft(spec, frames, B, Tmax)
+        return {"wave": wave, "wave_lens": wave_lens}
+
+    def stft(self, wave, wave_lens):
+        """(B, Nmax) fp32 -> {'spectrum': complex64 (B, 1 + Nmax // hop, bins), 'melspec_lens'}: the front end's transform with
+        its phases (framing, reflection, window and frame count as MelFrontEnd)"""
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        if wave.dim() != 2 or min(wave.shape) < 1:
+            raise ValueError(f"Vocoder: wave must be (B, Nmax), got {tuple(wave.shape)}")
+        if wave.size(1) < self.hop:
+            raise ValueError(f"Vocoder: wave needs Nmax >= hop_length = {self.hop} samples (two frames), got {tuple(wave.shape)}")
+        self._chk(wave, "wave", torch.float32)
+        B, Nmax = wave.shape
+        lens = self._lens(wave_lens, B, "wave_lens")
+        wave = wave.detach()
+        if (Nmax > 1 and wave.stride(1) != 1) or (B > 1 and wave.stride(0) < Nmax):
+            wave = wave.contiguous()
+        ld = wave.stride(0) if B > 1 else Nmax
+        Tmax = 1 + Nmax // self.hop
+        spec = torch.empty(B, Tmax, self.bins, 2, dtype=torch.float32, device=wave.device)
+        frames = torch.empty(B, dtype=torch.int64, device=wave.device)
+        _lib.check(_lib.load().ttts_stft_project(_p(wave), ld, _p(lens), None, B, Nmax, self.n_fft, self.hop, _p(self.front_end.tables),
+                                                 None, None, 0.0, _p(spec), _p(frames), _stream()), "ttts_stft_project")
+        return {"spectrum": torch.view_as_complex(spec), "melspec_lens": frames}
+
+    def _init(self, init, B, Tmax, seed):
+        import torch
+        if init is None:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(seed))
+            angle = torch.rand(B, Tmax, self.bins, generator=gen, dtype=torch.float32, device=self.device) * (2.0 * math.pi)
+            return torch.polar(torch.ones_like(angle), angle)
+        if tuple(init.shape) != (B, Tmax, self.bins):
+            raise ValueError(f"Vocoder: init must be (B, Tmax, bins) = ({B}, {Tmax}, {self.bins}), got {tuple(init.shape)}")
+        self._chk(init, "init", torch.complex64)
+        return init.detach()
+
+    def _griffin_lim(self, mag, frames, init, seed):
+        """mag: (B, Tmax, bins) fp32 contiguous; frames: the EFFECTIVE frames (int64, device)"""
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        B, Tmax, _ = mag.shape
+        init = self._init(init, B, Tmax, seed)
+        spec = torch.view_as_real(init * mag).contiguous()            # unit phases times the magnitudes, once per call
+        prev = torch.zeros_like(spec) if self.momentum > 0.0 and self.n_iter > 0 else None
+        lib, tables = _lib.load(), self.front_end.tables
+        Nmax = (Tmax - 1) * self.hop
+        for _ in range(self.n_iter):
+            wave, _lens = self._istft(spec, frames, B, Tmax)
+            _lib.check(lib.ttts_stft_project(_p(wave), Nmax, None, _p(frames), B, Nmax, self.n_fft, self.hop, _p(tables), _p(mag),
+                                             _p(prev), self.momentum if prev is not None else 0.0, _p(spec), None, _stream()),
+                       "ttts_stft_project")
+        wave, wave_lens = self._istft(spec, frames, B, Tmax)
+        return {"wave": wave, "wave_lens": wave_lens}
+
+    def griffin_lim(self, magnitude, frames, init=None, seed: int = 0):
+        """linear magnitudes (B, Tmax, bins) fp32 and the rows' frames -> {'wave', 'wave_lens'}; rows that cannot be vocoded
+        ((frames - 1) * hop <= n_fft/2) come back as 0 samples"""
+        import torch
+        self._frames3(magnitude, self.bins, "magnitudes", "magnitude")
+        self._chk(magnitude, "magnitude", torch.float32)
+        B, Tmax, _ = magnitude.shape
+        frames = self._lens(frames, B, "frames").clamp(0, Tmax)
+        frames = torch.where((frames - 1) * self.hop > self.n_fft // 2, frames, torch.zeros_like(frames))
+        return self._griffin_lim(magnitude.detach().contiguous(), frames, init, seed)
+
+    def __call__(self, melspec, melspec_lens, init=None, seed: int = 0):
+        m = self.magnitude(melspec, melspec_lens)
+        return self._griffin_lim(m["spectrogram"], m["melspec_lens"], init, seed)

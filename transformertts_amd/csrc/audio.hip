@@ -20,6 +20,7 @@
 // by the workgroup that owns them.  The statistics kernel adds x and x^2 of an utterance's valid rows in double, one
 // workgroup per utterance and a fixed tree: no atomics, the same bits every call.
 #include "fft_lds.h"
+#include "audio_common.h"
 #include "ttts_common.h"
 
 #include <math.h>
@@ -27,35 +28,9 @@
 namespace ttts {
 
 constexpr int AUDIO_FRAMES = 8;          // frames a workgroup carries
-constexpr int AUDIO_HEADER = 8;          // words in front of the tables
-constexpr uint32_t AUDIO_MAGIC = 0x4C454D54u;
 constexpr int AUDIO_MAX_NNZ = 4096;      // weights a workgroup stages in LDS (a triangular bank holds about 2 per bin)
-constexpr int AUDIO_MAX_MELS = 512;      // static + staged LDS stay under 64 KB at n_fft 2048
 
-// threads that share a frame: 8 samples and one or two butterflies of a stage per thread
-__host__ __device__ constexpr int audio_threads(int n_fft) { return n_fft / 8 < 64 ? 64 : n_fft / 8; }
-__host__ __device__ static inline bool audio_n_fft_ok(int n) { return n == 256 || n == 512 || n == 1024 || n == 2048; }
-// the table buffer in 4-byte words: header | window (n_fft) | roots re, im (M each) | w^k re, im (M/2 + 1 each) | first, count,
-// offset (n_mels each, int32) | weights (nnz)
-struct AudioTables {
-    long window, tw_re, tw_im, pw_re, pw_im, first, count, offset, weights, words;
-};
-__host__ __device__ static inline AudioTables audio_tables(int n_fft, int n_mels, int nnz) {
-    const long M = n_fft / 2;
-    AudioTables t;
-    t.window = AUDIO_HEADER;
-    t.tw_re = t.window + n_fft;
-    t.tw_im = t.tw_re + M;
-    t.pw_re = t.tw_im + M;
-    t.pw_im = t.pw_re + M / 2 + 1;
-    t.first = t.pw_im + M / 2 + 1;
-    t.count = t.first + n_mels;
-    t.offset = t.count + n_mels;
-    t.weights = t.offset + n_mels;
-    t.words = t.weights + nnz;
-    return t;
-}
-
+// (the table layout, audio_threads, the frame load and the real-FFT unpacking: audio_common.h, shared with vocoder.hip)
 template <int N>
 __global__ __launch_bounds__(audio_threads(N)) void logmel_kernel(const float* __restrict__ wave, long ld_batch,
                                                                   const int64_t* __restrict__ wave_lens, int Nmax, int hop, int Tmax,
@@ -89,19 +64,14 @@ __global__ __launch_bounds__(audio_threads(N)) void logmel_kernel(const float* _
     int32_t* f_count = f_first + n_mels;
     int32_t* f_off = f_count + n_mels;
     const AudioTables tb = audio_tables(N, n_mels, nnz);
-    for (int k = lane; k < M; k += THREADS) {
-        w_re[fft_pad(k)] = tables[tb.tw_re + k];
-        w_im[fft_pad(k)] = tables[tb.tw_im + k];
-    }
-    for (int k = lane; k < 2 * (M / 2 + 1); k += THREADS) pw_re[k] = tables[tb.pw_re + k];   // (re, im back to back)
+    audio_stage_roots<N>(tables, tb, w_re, w_im, pw_re, lane);
     if (mode == TTTS_AUDIO_LOGMEL) {                                 // (uniform)
         const int32_t* ti = reinterpret_cast<const int32_t*>(tables);
         for (int k = lane; k < 3 * n_mels; k += THREADS) f_first[k] = ti[tb.first + k];   // (count, offset behind it)
         for (int k = lane; k < nnz; k += THREADS) weights[k] = tables[tb.weights + k];
     }
     float win[PER_LANE];
-#pragma unroll
-    for (int i = 0; i < PER_LANE; ++i) win[i] = tables[tb.window + lane + THREADS * i];
+    audio_load_window<N>(tables, tb, win, lane);
     const bool norm = mean_std != nullptr && mode == TTTS_AUDIO_LOGMEL;
     const float mean = norm ? mean_std[0] : 0.f, sdev = norm ? mean_std[1] + 1e-8f : 1.f;
     const float* wb = wave + (long)b * ld_batch;
@@ -111,29 +81,12 @@ __global__ __launch_bounds__(audio_threads(N)) void logmel_kernel(const float* _
     float* mag = fft_result_in_second(M) ? a_re : b_re;
 
     for (int t = t0; t < tv; ++t) {
-        const int start = t * hop - M;
-#pragma unroll
-        for (int i = 0; i < PER_LANE; ++i) {
-            const int n = lane + THREADS * i;
-            int g = start + n;
-            g = g < 0 ? -g : g;
-            g = g >= len ? 2 * (len - 1) - g : g;
-            g = g < 0 ? 0 : g > len - 1 ? len - 1 : g;               // (never acts for len >= n_fft/2 + 1; keeps every load inside)
-            const float v = wb[g] * win[i];
-            ((n & 1) ? a_im : a_re)[fft_pad(n >> 1)] = v;
-        }
+        audio_load_frame<N>(wb, len, t * hop - M, win, a_re, a_im, lane);
         fft_lds<M, FFT_FORWARD, THREADS>(a_re, a_im, b_re, b_im, w_re, w_im, lane);
-        for (int k = lane; k <= M / 2; k += THREADS) {
-            const int m = (M - k) & (M - 1);
-            const float zkr = z_re[fft_pad(k)], zki = z_im[fft_pad(k)], zmr = z_re[fft_pad(m)], zmi = z_im[fft_pad(m)];
-            const float er = 0.5f * (zkr + zmr), ei = 0.5f * (zki - zmi);
-            const float dr = 0.5f * (zkr - zmr), di = 0.5f * (zki + zmi);
-            const float wr = pw_re[k], wi = pw_im[k];
-            const float pr = di * wr + dr * wi, pi = di * wi - dr * wr;         // w^k O, O = (di, -dr)
-            const float xr = er + pr, xi = ei + pi, yr = er - pr, yi = ei - pi;
+        audio_unpack_real<N>(z_re, z_im, pw_re, pw_im, lane, [&](int k, float xr, float xi, float yr, float yi) {
             mag[k] = sqrtf(xr * xr + xi * xi);
             mag[M - k] = sqrtf(yr * yr + yi * yi);
-        }
+        });
         __syncthreads();
         if (mode == TTTS_AUDIO_MAGNITUDE) {                          // (uniform)
             float* row = ob + (long)t * (M + 1);
