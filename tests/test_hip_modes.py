@@ -1223,3 +1223,38 @@ def test_dma_gemm_streams_across_tiles(M, N, K, raw):
         disturb()
         assert bwd(y2, residual=residual, gate=hgate) == 0
         assert torch.equal(y, y2)
+
+
+def test_conv_forward_and_data_gradient_forms_agree_with_fp64():
+    """The fp32-MFMA and bf16x6 Conv1d forward / data-gradient entry points (ttts_conv1d_fwd, ttts_conv1d_bwd_data and their _x6
+    forms), called directly and held to fp64 like the Linear entries of the same two kernels: every tap clipping at an utterance
+    edge with cin != cout (a swapped role shows), a ragged last tile over rows that cross utterance boundaries, and one row of
+    one tap.  Outputs start as NaN."""
+    from transformertts_amd import _lib, ops
+    from transformertts_amd.ops import _p, _stream
+    lib = _lib.load()
+    for B, T, cin, cout, taps in ((2, 5, 16, 32, 5), (3, 131, 32, 16, 3), (1, 1, 16, 16, 1)):
+        x, w, b = _rand(B, T, cin, seed=1), _rand(cout, cin, taps, seed=2, scale=(taps * cin) ** -0.5), _rand(cout, seed=3)
+        dy = _rand(B, T, cout, seed=4)
+        ref = torch.nn.functional.conv1d(x.double().transpose(1, 2), w.double(), b.double(), padding=taps // 2).transpose(1, 2)
+        xd = torch.zeros(B, T, cin, dtype=torch.float64, device=_dev(), requires_grad=True)
+        torch.nn.functional.conv1d(xd.transpose(1, 2), w.double(), None, padding=taps // 2).transpose(1, 2).backward(dy.double())
+        w_fwd, w_bwd = torch.empty(cout * taps * cin, device=_dev()), torch.empty(cin * taps * cout, device=_dev())
+        assert lib.ttts_conv1d_pack_weight(_p(w), _p(w_fwd), _p(w_bwd), cout, cin, taps, _stream()) == 0
+        for x6 in (False, True):
+            y = torch.full((B, T, cout), float("nan"), device=_dev())
+            dx = torch.full((B, T, cin), float("nan"), device=_dev())
+            if x6:
+                rc = lib.ttts_conv1d_fwd_x6(_p(x), _p(ops._planes(w, ops.X6_CONV_FWD, cout, taps * cin, cin, taps)), _p(b), _p(y), B, T,
+                                            cin, cout, taps, _stream())
+            else:
+                rc = lib.ttts_conv1d_fwd(_p(x), _p(w_fwd), _p(b), _p(y), B, T, cin, cout, taps, _stream())
+            print(f"conv fwd x6={x6} {(B, T, cin, cout, taps)}: rc {rc} rel_l2 {_rel(y, ref):.3e}")
+            assert rc == 0 and _rel(y, ref) < TOL, ("conv fwd", x6, B, T, cin, cout, taps, _rel(y, ref))
+            if x6:
+                rc = lib.ttts_conv1d_bwd_data_x6(_p(dy), _p(ops._planes(w, ops.X6_CONV_BWD, cin, taps * cout, cout, taps)), _p(dx), B, T,
+                                                 cin, cout, taps, _stream())
+            else:
+                rc = lib.ttts_conv1d_bwd_data(_p(dy), _p(w_bwd), _p(dx), B, T, cin, cout, taps, _stream())
+            print(f"conv dgrad x6={x6} {(B, T, cin, cout, taps)}: rc {rc} rel_l2 {_rel(dx, xd.grad):.3e}")
+            assert rc == 0 and _rel(dx, xd.grad) < TOL, ("conv dgrad", x6, B, T, cin, cout, taps, _rel(dx, xd.grad))

@@ -963,22 +963,6 @@ static int dispatch_wgrad_split(const GemmArgs& g, int zdim, int tile, hipStream
     }
 }
 
-static GemmArgs base_args() {
-    GemmArgs g;
-    g.A = g.B = nullptr; g.C = nullptr;
-    g.M = g.N = g.K = 0; g.lda = g.ldb = g.ldc = 0;
-    g.T = 0; g.cin = 1; g.shift0 = 0; g.shift_step = 0; g.ztaps = 1;
-    g.kt_per_split = 1 << 30; g.c_zstride = 0;
-    g.bias = nullptr; g.act = 0; g.drop_scale = 1.f; g.drop_thr = 0; g.seed = 0; g.step_seed = nullptr;
-    g.residual = nullptr; g.ldr = 0; g.colsum = nullptr; g.a_bytes = 0; g.b_bytes = 0;
-    g.relu_out = nullptr; g.relu_scale = 1.f;
-    g.a_amax = nullptr; g.a_amax_n = 0; g.b_amax = nullptr; g.b_amax_n = 0; g.c_amax = nullptr; g.bn_ws = nullptr;
-    g.a_row_inv = nullptr; g.c_row_inv = nullptr; g.c_amax_sec = 0;
-    return g;
-}
-
-static int aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // how the row (reduction) dimension of a weight gradient is split.  The fp32-MFMA / bf16x6 kernels aim at about 768
 // workgroups (3 per CU).  The fp16x3 kernel holds two workgroups per CU, so 768 is one full round plus a half-empty one;
 // it gets ONE round -- 512 workgroups for outputs of more than 12 tiles over long row ranges, else 256: every split costs
@@ -1037,44 +1021,6 @@ static bool wgrad_use_x6(int N, int K) { return (N >= 128 || N == 80 || N == 96)
 using namespace ttts;
 
 extern "C" {
-
-int ttts_linear_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y, int64_t M,
-                    int N, int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed, int row_shift, int T, void* stream) {
-    TTTS_REQUIRE(x && w && y, "linear_fwd: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_fwd: bad dims M=%lld N=%d K=%d", (long long)M, N, K);
-    TTTS_REQUIRE(K % BK == 0, "linear_fwd: K=%d must be a multiple of %d", K, BK);
-    TTTS_REQUIRE(aligned16(x) && aligned16(w), "linear_fwd: x/w must be 16-byte aligned");
-    TTTS_REQUIRE(act == 0 || act == 1, "linear_fwd: act must be 0 (none) or 1 (relu)");
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "linear_fwd: dropout p=%f out of [0,1)", drop_p);
-    TTTS_REQUIRE(row_shift == 0 || (T > 0 && M % T == 0), "linear_fwd: row_shift needs T>0 and M %% T == 0");
-    GemmArgs g = base_args();
-    g.A = x; g.B = w; g.C = y; g.M = (int)M; g.N = N; g.K = K;
-    g.lda = K; g.ldb = K; g.ldc = N;
-    TTTS_REQUIRE((uint64_t)M * K * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_fwd: operand larger than 4 GiB");
-    g.a_bytes = (uint32_t)((uint64_t)M * K * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.cin = K; g.shift0 = row_shift; g.T = (row_shift != 0) ? T : 0;
-    g.bias = bias; g.act = act;
-    if (drop_p > 0.f) { g.drop_thr = drop_threshold(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.seed = seed; g.step_seed = step_seed; }
-    g.residual = residual; g.ldr = N;
-    return dispatch_gemm<true, true>(g, 1, TILE_AUTO, (hipStream_t)stream);
-}
-
-int ttts_linear_bwd_data(const float* dy, const float* w, const float* residual, float* dx, int64_t M, int N, int K,
-                         const float* relu_out, float relu_scale, void* stream) {
-    // dx[M,K] = dy[M,N] . w[N,K] (+ residual)   (reduction over N; w consumed in its natural [N][K] layout)
-    TTTS_REQUIRE(dy && w && dx, "linear_bwd_data: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_bwd_data: bad dims");
-    TTTS_REQUIRE(N % BK == 0 && K % 4 == 0, "linear_bwd_data: N=%d must be a multiple of 16 and K=%d of 4", N, K);
-    TTTS_REQUIRE(aligned16(dy) && aligned16(w), "linear_bwd_data: dy/w must be 16-byte aligned");
-    GemmArgs g = base_args();
-    g.A = dy; g.B = w; g.C = dx; g.M = (int)M; g.N = K; g.K = N;
-    g.lda = N; g.ldb = K; g.ldc = K; g.cin = N;
-    TTTS_REQUIRE((uint64_t)M * N * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_bwd_data: operand larger than 4 GiB");
-    g.a_bytes = (uint32_t)((uint64_t)M * N * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.residual = residual; g.ldr = K;
-    g.relu_out = relu_out; g.relu_scale = relu_scale;
-    return dispatch_gemm<true, false>(g, 1, TILE_AUTO, (hipStream_t)stream);
-}
 
 size_t ttts_wgrad_workspace_bytes(int64_t M, int N, int K, int taps) {
     // covers both kernel forms (their row-split counts differ)
@@ -1291,40 +1237,6 @@ int ttts_conv1d_pack_weight(const float* w, float* w_fwd, float* w_bwd, int cout
     return TTTS_OK;
 }
 
-int ttts_conv1d_fwd(const float* x, const float* w_fwd, const float* bias, float* y, int B, int T, int cin, int cout,
-                    int taps, void* stream) {
-    // y[b,t,co] = bias[co] + sum_{tap,ci} x[b,t+tap-pad,ci] * w[co,ci,tap],  pad = (taps-1)/2, zero outside [0,T)
-    TTTS_REQUIRE(x && w_fwd && y, "conv1d_fwd: null pointer");
-    TTTS_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "conv1d_fwd: bad dims");
-    TTTS_REQUIRE(cin % BK == 0, "conv1d_fwd: cin=%d must be a multiple of %d", cin, BK);
-    TTTS_REQUIRE((long)B * T < (1L << 31), "conv1d_fwd: B*T too large");
-    TTTS_REQUIRE(aligned16(x) && aligned16(w_fwd), "conv1d_fwd: pointers must be 16-byte aligned");
-    GemmArgs g = base_args();
-    g.A = x; g.B = w_fwd; g.C = y; g.M = B * T; g.N = cout; g.K = taps * cin;
-    g.lda = cin; g.ldb = (long)taps * cin; g.ldc = cout;
-    TTTS_REQUIRE((uint64_t)B * T * cin * 4 < (1ull << 32), "conv1d_fwd: activation larger than 4 GiB");
-    g.a_bytes = (uint32_t)((uint64_t)B * T * cin * 4); g.b_bytes = (uint32_t)((uint64_t)cout * taps * cin * 4);
-    g.T = T; g.cin = cin; g.shift0 = -((taps - 1) / 2); g.shift_step = 1;
-    g.bias = bias;
-    return dispatch_gemm<true, true>(g, 1, TILE_AUTO, (hipStream_t)stream);
-}
-
-int ttts_conv1d_bwd_data(const float* dy, const float* w_bwd, float* dx, int B, int T, int cin, int cout, int taps,
-                         void* stream) {
-    // dx[b,t,ci] = sum_{tap,co} dy[b,t-tap+pad,co] * w[co,ci,tap]   (w_bwd = w packed as [ci][tap][co])
-    TTTS_REQUIRE(dy && w_bwd && dx, "conv1d_bwd_data: null pointer");
-    TTTS_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "conv1d_bwd_data: bad dims");
-    TTTS_REQUIRE(cout % BK == 0, "conv1d_bwd_data: cout=%d must be a multiple of %d", cout, BK);
-    TTTS_REQUIRE(aligned16(dy) && aligned16(w_bwd), "conv1d_bwd_data: pointers must be 16-byte aligned");
-    GemmArgs g = base_args();
-    g.A = dy; g.B = w_bwd; g.C = dx; g.M = B * T; g.N = cin; g.K = taps * cout;
-    g.lda = cout; g.ldb = (long)taps * cout; g.ldc = cin;
-    TTTS_REQUIRE((uint64_t)B * T * cout * 4 < (1ull << 32), "conv1d_bwd_data: activation larger than 4 GiB");
-    g.a_bytes = (uint32_t)((uint64_t)B * T * cout * 4); g.b_bytes = (uint32_t)((uint64_t)cin * taps * cout * 4);
-    g.T = T; g.cin = cout; g.shift0 = (taps - 1) / 2; g.shift_step = -1;
-    return dispatch_gemm<true, true>(g, 1, TILE_AUTO, (hipStream_t)stream);
-}
-
 static int conv1d_bwd_weight_impl(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
                                   int T, int cin, int cout, int taps, int accumulate, bool x6, ttts_reduce_queue* queue,
                                   void* stream_, const float* dy_amax = nullptr, const float* x_amax = nullptr) {
@@ -1428,55 +1340,6 @@ int ttts_weight_split_batched(const int64_t* descs, int n, int64_t total_blocks,
     return TTTS_OK;
 }
 
-int ttts_linear_fwd_x6(const float* x, const void* w_planes, const float* bias, const float* residual, float* y,
-                       int64_t M, int N, int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed, int row_shift, int T, void* stream) {
-    TTTS_REQUIRE(x && w_planes && y, "linear_fwd_x6: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_fwd_x6: bad dims");
-    TTTS_REQUIRE(K % BK == 0, "linear_fwd_x6: K=%d must be a multiple of %d", K, BK);
-    TTTS_REQUIRE(aligned16(x) && aligned16(w_planes), "linear_fwd_x6: x / planes must be 16-byte aligned");
-    TTTS_REQUIRE(act == 0 || act == 1, "linear_fwd_x6: act must be 0 (none) or 1 (relu)");
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "linear_fwd_x6: dropout p out of [0,1)");
-    TTTS_REQUIRE(row_shift == 0 || (T > 0 && M % T == 0), "linear_fwd_x6: row_shift needs T>0 and M %% T == 0");
-    TTTS_REQUIRE((uint64_t)M * K * 4 < (1ull << 32) && (uint64_t)N * K * 6 < (1ull << 32), "linear_fwd_x6: operand larger than 4 GiB");
-    GemmArgs g = base_args();
-    g.A = x; g.B = (const float*)w_planes; g.C = y; g.M = (int)M; g.N = N; g.K = K;
-    g.lda = K; g.ldb = K; g.ldc = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * K * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 6);
-    g.cin = K; g.shift0 = row_shift; g.T = (row_shift != 0) ? T : 0;
-    g.bias = bias; g.act = act;
-    if (drop_p > 0.f) { g.drop_thr = drop_threshold(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.seed = seed; g.step_seed = step_seed; }
-    g.residual = residual; g.ldr = N;
-    return dispatch_split(g, (hipStream_t)stream);
-}
-
-int ttts_linear_fwd_h3(const float* x, const void* w_planes, const float* bias, const float* residual, float* y,
-                       int64_t M, int N, int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed, int row_shift,
-                       int T, const float* x_amax, float* y_amax_out, void* stream) {
-    TTTS_REQUIRE(x && w_planes && y && x_amax, "linear_fwd_h3: null pointer (x_amax, the partial maxima of |x|, is required)");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_fwd_h3: bad dims");
-    TTTS_REQUIRE(K % 4 == 0 && N % 4 == 0, "linear_fwd_h3: K=%d and N=%d must be multiples of 4", K, N);
-    TTTS_REQUIRE(aligned16(x) && aligned16(w_planes), "linear_fwd_h3: x / planes must be 16-byte aligned");
-    TTTS_REQUIRE(act == 0 || act == 1, "linear_fwd_h3: act must be 0 (none) or 1 (relu)");
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "linear_fwd_h3: dropout p out of [0,1)");
-    TTTS_REQUIRE(row_shift == 0 || (T > 0 && M % T == 0), "linear_fwd_h3: row_shift needs T>0 and M %% T == 0");
-    TTTS_REQUIRE((uint64_t)M * K * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_fwd_h3: operand larger than 4 GiB");
-    GemmArgs g = base_args();
-    // (K is padded to the image's 32-deep k-tiles: the loader reads up to 28 floats past a row's end -- the next row, or
-    // zeros past the buffer -- against zero weight columns)
-    const int Kp = h3_pad32(K);
-    g.A = x; g.B = (const float*)w_planes; g.C = y; g.M = (int)M; g.N = N; g.K = Kp;
-    g.lda = K; g.ldb = Kp; g.ldc = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * K * 4); g.b_bytes = (uint32_t)((uint64_t)N * Kp * 4);
-    g.cin = Kp; g.shift0 = row_shift; g.T = (row_shift != 0) ? T : 0;
-    g.bias = bias; g.act = act;
-    if (drop_p > 0.f) { g.drop_thr = drop_threshold(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.seed = seed; g.step_seed = step_seed; }
-    g.residual = residual; g.ldr = N;
-    g.a_amax = x_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(w_planes, N, Kp); g.b_amax_n = 1;
-    g.c_amax = y_amax_out;
-    return dispatch_h3(g, (hipStream_t)stream);
-}
-
 int ttts_conv1d_fwd_h3_bn_blocks(int B, int T, int cin, int cout, int taps) {
     return h3_bn_blocks((long)B * T, cout, (long)taps * h3_pad32(cin));
 }
@@ -1488,114 +1351,222 @@ int ttts_conv1d_fwd_h3_bn_chunk_rows(int B, int T, int cin, int cout, int taps) 
     return h3_bn_blocks((long)B * T, cout, (long)taps * h3_pad32(cin)) > 0 ? h3_bn_chunk_rows((long)B * T, cout, (long)taps * h3_pad32(cin)) : 0;
 }
 
-int ttts_conv1d_fwd_h3(const float* x, const void* planes_fwd, const float* bias, float* y, int B, int T, int cin, int cout,
-                       int taps, const float* x_amax, float* bn_partials, void* stream) {
-    TTTS_REQUIRE(x && planes_fwd && y && x_amax, "conv1d_fwd_h3: null pointer (x_amax, the partial maxima of |x|, is required)");
-    TTTS_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "conv1d_fwd_h3: bad dims");
-    TTTS_REQUIRE(cin % 4 == 0 && cout % 4 == 0, "conv1d_fwd_h3: cin=%d and cout=%d must be multiples of 4", cin, cout);
-    TTTS_REQUIRE((uint64_t)B * T * cin * 4 < (1ull << 32), "conv1d_fwd_h3: activation larger than 4 GiB");
-    TTTS_REQUIRE(aligned16(x) && aligned16(planes_fwd), "conv1d_fwd_h3: pointers must be 16-byte aligned");
-    GemmArgs g = base_args();
-    const int cinp = h3_pad32(cin);                  // channels per tap of the padded image (see ttts_linear_fwd_h3)
-    g.A = x; g.B = (const float*)planes_fwd; g.C = y; g.M = B * T; g.N = cout; g.K = taps * cinp;
-    g.lda = cin; g.ldb = (long)taps * cinp; g.ldc = cout;
-    g.a_bytes = (uint32_t)((uint64_t)B * T * cin * 4); g.b_bytes = (uint32_t)((uint64_t)cout * taps * cinp * 4);
-    g.T = T; g.cin = cinp; g.shift0 = -((taps - 1) / 2); g.shift_step = 1;
-    g.bias = bias;
-    g.a_amax = x_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(planes_fwd, cout, (long)taps * cinp); g.b_amax_n = 1;
-    TTTS_REQUIRE(bn_partials == nullptr || (((uintptr_t)bn_partials) & 15) == 0, "conv1d_fwd_h3: bn_partials must be 16-byte aligned");
-    g.bn_ws = bn_partials;
-    return dispatch_h3(g, (hipStream_t)stream);
+// ---------------------------------------------------------------------------------------------------------------
+// The 17 forward-type entry points: Linear and Conv1d, forward and data gradient, in six FORMS.  All of them are the problem
+// C[rows][width] = A[rows][depth (x taps, row-shifted)] . B[width][taps x depth]: three bodies below state the argument checks
+// and the GemmArgs once, the entries name their form and pass empty operands for what they lack.
+enum GemmForm {
+    FORM_F32,       // fp32 MFMA (gemm.hip): fp32 weight as it is
+    FORM_X6,        // bf16x6 (gemm.hip): three bf16 weight planes, 6 bytes per element
+    FORM_H3,        // fp16x3 (gemm_h3.hip): two f16 planes whose depth is padded to 32, the activation's partial maxima
+    FORM_H3I,       // fp16x3 on the LDS-DMA kernel (gemm_h3i.hip), activation IMAGE + per-row inverse scales; K16-major weight image
+    FORM_H3D,       // ... with a plain fp32 activation and its partial maxima
+    FORM_H3D_IMG    // ... and a HEAD-IMAGE output
+};
+static int form_depth_mult(GemmForm f) { return f <= FORM_X6 ? BK : f == FORM_H3 ? 4 : 32; }
+static int form_width_mult(GemmForm f) { return f <= FORM_X6 ? 1 : f == FORM_H3D_IMG ? 64 : 4; }
+static bool form_takes_amax(GemmForm f) { return f == FORM_H3 || f >= FORM_H3D; }
+
+#define ENTRY_REQUIRE(cond, fmt, ...) TTTS_REQUIRE(cond, "%s: " fmt, name, ##__VA_ARGS__)
+
+// the checks every body makes once it knows its rows, reduction depth and output width (dn / wn: what the entry calls them)
+static int entry_check_shape(const char* name, GemmForm f, const void* a, const void* b, const void* c, int64_t rows, int depth,
+                             const char* dn, int width, const char* wn, int wmult, int taps) {
+    const int dmult = form_depth_mult(f);
+    if (wmult == 1) ENTRY_REQUIRE(depth % dmult == 0, "%s=%d must be a multiple of %d", dn, depth, dmult);
+    ENTRY_REQUIRE(depth % dmult == 0 && width % wmult == 0, "%s=%d must be a multiple of %d and %s=%d of %d", dn, depth, dmult, wn,
+                  width, wmult);
+    // (the LDS-DMA kernels store whole 16-byte pieces through a descriptor on the output as well)
+    ENTRY_REQUIRE(aligned16(a) && aligned16(b) && (f < FORM_H3I || aligned16(c)), "pointers must be 16-byte aligned");
+    const uint64_t w_bytes = (uint64_t)width * depth * (f == FORM_X6 ? 6 : 4);      // (the unpadded extent, per tap)
+    ENTRY_REQUIRE((uint64_t)rows * depth * 4 < (1ull << 32) && w_bytes < (1ull << 32) && w_bytes * taps < (1ull << 32),
+                  "operand larger than 4 GiB");
+    return TTTS_OK;
 }
 
-int ttts_linear_bwd_data_h3(const float* dy, const void* wt_planes, const float* residual, float* dx, int64_t M, int N,
-                            int K, const float* relu_out, float relu_scale, const float* dy_amax, float* dx_amax_out,
-                            void* stream) {
-    // dx[M,K] = dy[M,N] . w[N,K] (+ residual) in the fp16x3 form; wt_planes = weight_split mode 5 (w^T as [K][N] rows);
-    // dy_amax = the partial maxima of |dy| written by ttts_amax_partials (the dynamic pre-scale of the gradient operand)
-    TTTS_REQUIRE(dy && wt_planes && dx && dy_amax, "linear_bwd_data_h3: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_bwd_data_h3: bad dims");
-    TTTS_REQUIRE(N % 4 == 0 && K % 4 == 0, "linear_bwd_data_h3: N=%d and K=%d must be multiples of 4", N, K);
-    TTTS_REQUIRE(aligned16(dy) && aligned16(wt_planes), "linear_bwd_data_h3: pointers must be 16-byte aligned");
-    TTTS_REQUIRE((uint64_t)M * N * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_bwd_data_h3: operand larger than 4 GiB");
+// A: rows x depth, B: width rows of taps x depth (fp16x3: x the depth padded to the image's 32-deep k-tiles -- the loader reads
+// up to 28 floats past a row's end, the next row or zeros past the buffer, against zero weight columns), C: rows x width
+static GemmArgs entry_args(GemmForm f, const void* a, const void* b, void* c, int64_t rows, int depth, int width, int taps,
+                           const float* a_amax, const float* a_row_inv, float* c_amax) {
     GemmArgs g = base_args();
-    const int Np = h3_pad32(N);                      // reduction depth of the padded image (see ttts_linear_fwd_h3)
-    g.A = dy; g.B = (const float*)wt_planes; g.C = dx; g.M = (int)M; g.N = K; g.K = Np;
-    g.lda = N; g.ldb = Np; g.ldc = K; g.cin = Np;
-    g.a_bytes = (uint32_t)((uint64_t)M * N * 4); g.b_bytes = (uint32_t)((uint64_t)Np * K * 4);
+    const int dp = f == FORM_H3 ? h3_pad32(depth) : depth;
+    g.A = (const float*)a; g.B = (const float*)b; g.C = (float*)c;
+    g.M = (int)rows; g.N = width; g.K = taps * dp;
+    g.lda = depth; g.ldb = (long)taps * dp; g.ldc = width; g.cin = dp;
+    g.a_bytes = (uint32_t)((uint64_t)rows * depth * 4);
+    g.b_bytes = (uint32_t)((uint64_t)width * taps * dp * (f == FORM_X6 ? 6 : 4));
+    if (form_takes_amax(f)) { g.a_amax = a_amax; g.a_amax_n = H3_AMAX_PARTIALS; }
+    if (f >= FORM_H3) { g.b_amax = h3_plane_tail(b, width, (long)taps * dp); g.b_amax_n = 1; }
+    g.a_row_inv = a_row_inv;
+    g.c_amax = c_amax;
+    return g;
+}
+
+static int entry_dispatch(GemmForm f, const GemmArgs& g, void* stream, bool b_kc = true) {
+    switch (f) {
+        case FORM_F32: return b_kc ? dispatch_gemm<true, true>(g, 1, TILE_AUTO, (hipStream_t)stream)
+                                   : dispatch_gemm<true, false>(g, 1, TILE_AUTO, (hipStream_t)stream);
+        case FORM_X6: return dispatch_split(g, (hipStream_t)stream);
+        case FORM_H3: return dispatch_h3(g, (hipStream_t)stream);
+        default: return dispatch_h3i(g, (hipStream_t)stream);
+    }
+}
+
+// y[M,N] = drop(act(x[M,K] . w[N,K]^T + bias)) + residual; row_shift: x read that many rows further inside utterances of T rows
+static int linear_fwd_impl(const char* name, GemmForm f, const void* x, const float* x_row_inv, const void* w, const float* bias,
+                           const float* residual, void* y, float* y_row_inv, int64_t M, int N, int K, int act, float drop_p,
+                           uint64_t seed, const uint64_t* step_seed, int row_shift, int T, const float* x_amax, float* y_amax_out,
+                           int amax_section_cols, void* stream) {
+    ENTRY_REQUIRE(x && w && y && (!form_takes_amax(f) || x_amax) && (f != FORM_H3I || x_row_inv) && (f != FORM_H3D_IMG || y_row_inv),
+                  "null pointer");
+    ENTRY_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "bad dims M=%lld N=%d K=%d", (long long)M, N, K);
+    if (int rc = entry_check_shape(name, f, x, w, y, M, K, "K", N, "N", form_width_mult(f), 1)) return rc;
+    ENTRY_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (relu)");
+    ENTRY_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "dropout p=%f out of [0,1)", drop_p);
+    ENTRY_REQUIRE(row_shift == 0 || (T > 0 && M % T == 0), "row_shift needs T>0 and M %% T == 0");
+    ENTRY_REQUIRE(amax_section_cols >= 0 && (amax_section_cols == 0 || (amax_section_cols % 64 == 0 && N % amax_section_cols == 0)),
+                  "amax sections must be whole heads that divide N");
+    GemmArgs g = entry_args(f, x, w, y, M, K, N, 1, x_amax, x_row_inv, y_amax_out);
+    g.shift0 = row_shift; g.T = (row_shift != 0) ? T : 0;
+    g.bias = bias; g.act = act;
+    if (drop_p > 0.f) { g.drop_thr = drop_threshold(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.seed = seed; g.step_seed = step_seed; }
+    g.residual = residual; g.ldr = N;
+    g.c_row_inv = y_row_inv; g.c_amax_sec = amax_section_cols;
+    return entry_dispatch(f, g, stream);
+}
+
+// dx[M,K] = dy[M,N] . w[N,K] (+ residual), times the relu mask of relu_out and relu_scale (reduction over N).  The fp32 form
+// takes w in its natural [N][K] layout; the others its transposed image (ttts_weight_split modes 1 / 5 / 9: [K][N] rows)
+static int linear_bwd_data_impl(const char* name, GemmForm f, const void* dy, const float* dy_row_inv, const void* w,
+                                const float* residual, float* dx, int64_t M, int N, int K, const float* relu_out, float relu_scale,
+                                const float* dy_amax, float* dx_amax_out, void* stream) {
+    ENTRY_REQUIRE(dy && w && dx && (!form_takes_amax(f) || dy_amax) && (f != FORM_H3I || dy_row_inv), "null pointer");
+    ENTRY_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "bad dims M=%lld N=%d K=%d", (long long)M, N, K);
+    // (fp32: the natural-layout weight is read four neighbouring columns at a time)
+    if (int rc = entry_check_shape(name, f, dy, w, dx, M, N, "N", K, "K", f == FORM_F32 ? 4 : form_width_mult(f), 1)) return rc;
+    GemmArgs g = entry_args(f, dy, w, dx, M, N, K, 1, dy_amax, dy_row_inv, dx_amax_out);
+    if (f == FORM_F32) g.ldb = K;
     g.residual = residual; g.ldr = K;
     g.relu_out = relu_out; g.relu_scale = relu_scale;
-    g.a_amax = dy_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(wt_planes, K, Np); g.b_amax_n = 1;
-    g.c_amax = dx_amax_out;
-    return dispatch_h3(g, (hipStream_t)stream);
+    return entry_dispatch(f, g, stream, f != FORM_F32);
 }
 
-int ttts_conv1d_bwd_data_h3(const float* dy, const void* planes_bwd, float* dx, int B, int T, int cin, int cout, int taps,
-                            const float* dy_amax, void* stream) {
-    TTTS_REQUIRE(dy && planes_bwd && dx && dy_amax, "conv1d_bwd_data_h3: null pointer");
-    TTTS_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "conv1d_bwd_data_h3: bad dims");
-    TTTS_REQUIRE(cout % 4 == 0 && cin % 4 == 0, "conv1d_bwd_data_h3: cout=%d and cin=%d must be multiples of 4", cout, cin);
-    TTTS_REQUIRE((uint64_t)B * T * cout * 4 < (1ull << 32), "conv1d_bwd_data_h3: activation larger than 4 GiB");
-    TTTS_REQUIRE(aligned16(dy) && aligned16(planes_bwd), "conv1d_bwd_data_h3: pointers must be 16-byte aligned");
-    GemmArgs g = base_args();
-    const int coutp = h3_pad32(cout);                // channels per tap of the padded image (see ttts_linear_fwd_h3)
-    g.A = dy; g.B = (const float*)planes_bwd; g.C = dx; g.M = B * T; g.N = cin; g.K = taps * coutp;
-    g.lda = cout; g.ldb = (long)taps * coutp; g.ldc = cin;
-    g.a_bytes = (uint32_t)((uint64_t)B * T * cout * 4); g.b_bytes = (uint32_t)((uint64_t)cin * taps * coutp * 4);
-    g.T = T; g.cin = coutp; g.shift0 = (taps - 1) / 2; g.shift_step = -1;
-    g.a_amax = dy_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(planes_bwd, cin, (long)taps * coutp); g.b_amax_n = 1;
-    return dispatch_h3(g, (hipStream_t)stream);
-}
-
-int ttts_linear_bwd_data_x6(const float* dy, const void* wt_planes, const float* residual, float* dx, int64_t M, int N,
-                            int K, const float* relu_out, float relu_scale, void* stream) {
-    // dx[M,K] = dy[M,N] . w[N,K] (+ residual); wt_planes = split of w^T, i.e. [K][N] rows (weight_split mode 1)
-    TTTS_REQUIRE(dy && wt_planes && dx, "linear_bwd_data_x6: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_bwd_data_x6: bad dims");
-    TTTS_REQUIRE(N % BK == 0, "linear_bwd_data_x6: N=%d must be a multiple of 16", N);
-    TTTS_REQUIRE(aligned16(dy) && aligned16(wt_planes), "linear_bwd_data_x6: pointers must be 16-byte aligned");
-    TTTS_REQUIRE((uint64_t)M * N * 4 < (1ull << 32) && (uint64_t)N * K * 6 < (1ull << 32), "linear_bwd_data_x6: operand larger than 4 GiB");
-    GemmArgs g = base_args();
-    g.A = dy; g.B = (const float*)wt_planes; g.C = dx; g.M = (int)M; g.N = K; g.K = N;
-    g.lda = N; g.ldb = N; g.ldc = K; g.cin = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * N * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 6);
-    g.residual = residual; g.ldr = K;
-    g.relu_out = relu_out; g.relu_scale = relu_scale;
-    return dispatch_split(g, (hipStream_t)stream);
-}
-
-int ttts_conv1d_fwd_x6(const float* x, const void* planes_fwd, const float* bias, float* y, int B, int T, int cin, int cout,
-                       int taps, void* stream) {
-    TTTS_REQUIRE(x && planes_fwd && y, "conv1d_fwd_x6: null pointer");
-    TTTS_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "conv1d_fwd_x6: bad dims");
-    TTTS_REQUIRE(cin % BK == 0, "conv1d_fwd_x6: cin=%d must be a multiple of %d", cin, BK);
-    TTTS_REQUIRE((uint64_t)B * T * cin * 4 < (1ull << 32), "conv1d_fwd_x6: activation larger than 4 GiB");
-    TTTS_REQUIRE(aligned16(x) && aligned16(planes_fwd), "conv1d_fwd_x6: pointers must be 16-byte aligned");
-    GemmArgs g = base_args();
-    g.A = x; g.B = (const float*)planes_fwd; g.C = y; g.M = B * T; g.N = cout; g.K = taps * cin;
-    g.lda = cin; g.ldb = (long)taps * cin; g.ldc = cout;
-    g.a_bytes = (uint32_t)((uint64_t)B * T * cin * 4); g.b_bytes = (uint32_t)((uint64_t)cout * taps * cin * 6);
-    g.T = T; g.cin = cin; g.shift0 = -((taps - 1) / 2); g.shift_step = 1;
+// same-padded Conv1d over (b, t) rows, zero outside [0, T), pad = (taps - 1) / 2:
+//   forward        y[b,t,co]  = bias[co] + sum_{tap,ci} x[b,t+tap-pad,ci] * w[co,ci,tap]     (planes: [co][tap * cin + ci])
+//   data gradient  dx[b,t,ci] = sum_{tap,co} dy[b,t-tap+pad,co] * w[co,ci,tap]               (planes: [ci][tap * cout + co])
+// -- one problem with the sign of the tap shift and the roles of cin and cout exchanged
+static int conv1d_impl(const char* name, GemmForm f, bool fwd, const void* a, const void* planes, const float* bias, float* c, int B,
+                       int T, int cin, int cout, int taps, const float* a_amax, float* bn_partials, void* stream) {
+    ENTRY_REQUIRE(a && planes && c && (!form_takes_amax(f) || a_amax), "null pointer");
+    ENTRY_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "bad dims B=%d T=%d cin=%d cout=%d taps=%d", B, T,
+                  cin, cout, taps);
+    ENTRY_REQUIRE((long)B * T < (1L << 31), "B*T too large");
+    const int depth = fwd ? cin : cout, width = fwd ? cout : cin, pad = (taps - 1) / 2;
+    if (int rc = entry_check_shape(name, f, a, planes, c, (int64_t)B * T, depth, fwd ? "cin" : "cout", width, fwd ? "cout" : "cin",
+                                   form_width_mult(f), taps))
+        return rc;
+    ENTRY_REQUIRE(aligned16(bn_partials), "bn_partials must be 16-byte aligned");
+    GemmArgs g = entry_args(f, a, planes, c, (int64_t)B * T, depth, width, taps, a_amax, nullptr, nullptr);
+    g.T = T; g.shift0 = fwd ? -pad : pad; g.shift_step = fwd ? 1 : -1;
     g.bias = bias;
-    return dispatch_split(g, (hipStream_t)stream);
+    g.bn_ws = bn_partials;          // NULL, or the workspace of ttts_bn_train_stats (fp16x3 forward only)
+    return entry_dispatch(f, g, stream);
+}
+#undef ENTRY_REQUIRE
+
+int ttts_linear_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y, int64_t M, int N, int K,
+                    int act, float drop_p, uint64_t seed, const uint64_t* step_seed, int row_shift, int T, void* stream) {
+    return linear_fwd_impl("linear_fwd", FORM_F32, x, nullptr, w, bias, residual, y, nullptr, M, N, K, act, drop_p, seed, step_seed,
+                           row_shift, T, nullptr, nullptr, 0, stream);
+}
+int ttts_linear_fwd_x6(const float* x, const void* w_planes, const float* bias, const float* residual, float* y, int64_t M, int N,
+                       int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed, int row_shift, int T, void* stream) {
+    return linear_fwd_impl("linear_fwd_x6", FORM_X6, x, nullptr, w_planes, bias, residual, y, nullptr, M, N, K, act, drop_p, seed,
+                           step_seed, row_shift, T, nullptr, nullptr, 0, stream);
+}
+// x_amax: the partial maxima of |x| (ttts_amax_partials or a producer's `*_amax_out`); y_amax_out: NULL, or where max|y| goes
+int ttts_linear_fwd_h3(const float* x, const void* w_planes, const float* bias, const float* residual, float* y, int64_t M, int N,
+                       int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed, int row_shift, int T,
+                       const float* x_amax, float* y_amax_out, void* stream) {
+    return linear_fwd_impl("linear_fwd_h3", FORM_H3, x, nullptr, w_planes, bias, residual, y, nullptr, M, N, K, act, drop_p, seed,
+                           step_seed, row_shift, T, x_amax, y_amax_out, 0, stream);
+}
+int ttts_linear_fwd_h3i(const void* x_image, const float* x_row_inv, const void* w_planes, const float* bias, const float* residual,
+                        float* y, int64_t M, int N, int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed,
+                        float* y_amax_out, void* stream) {
+    return linear_fwd_impl("linear_fwd_h3i", FORM_H3I, x_image, x_row_inv, w_planes, bias, residual, y, nullptr, M, N, K, act, drop_p,
+                           seed, step_seed, 0, 0, nullptr, y_amax_out, 0, stream);
+}
+/* fp32 activation (per-tensor scale from its partial maxima) on the LDS-DMA kernel: the weight image is the K16-major one
+ * (ttts_weight_split modes 8 / 9); arguments otherwise as ttts_linear_fwd_h3 / ttts_linear_bwd_data_h3 without a row shift */
+int ttts_linear_fwd_h3d(const float* x, const void* w_planes, const float* bias, const float* residual, float* y, int64_t M, int N,
+                        int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed, const float* x_amax,
+                        float* y_amax_out, void* stream) {
+    return linear_fwd_impl("linear_fwd_h3d", FORM_H3D, x, nullptr, w_planes, bias, residual, y, nullptr, M, N, K, act, drop_p, seed,
+                           step_seed, 0, 0, x_amax, y_amax_out, 0, stream);
+}
+/* The in-projections of nn.MultiheadAttention (packed q/k/v, or its q and k/v row slices: torch/nn/functional.py:6206+ reached
+ * from model/layers.py:54-74 and torch _sa_block) with a HEAD-IMAGE output: y_image has the geometry of the fp32 output (M rows of
+ * N 4-byte cells) but holds, per row and 64-column head, {64 f16 hi, 64 f16 lo} of (x W^T + b) * 2^e(row, head);
+ * y_row_inv[head * M + row] = 2^-e.  y_amax_out: NULL, or N / amax_section_cols caller-zeroed TTTS_AMAX_SLOTS-float arrays (one per
+ * section: q / k / v), each receiving max|y| of its section. */
+int ttts_linear_fwd_h3d_img(const float* x, const void* w_planes, const float* bias, void* y_image, float* y_row_inv, int64_t M,
+                            int N, int K, const float* x_amax, float* y_amax_out, int amax_section_cols, void* stream) {
+    return linear_fwd_impl("linear_fwd_h3d_img", FORM_H3D_IMG, x, nullptr, w_planes, bias, nullptr, y_image, y_row_inv, M, N, K, 0, 0.f,
+                           0, nullptr, 0, 0, x_amax, y_amax_out, amax_section_cols, stream);
 }
 
+int ttts_linear_bwd_data(const float* dy, const float* w, const float* residual, float* dx, int64_t M, int N, int K,
+                         const float* relu_out, float relu_scale, void* stream) {
+    return linear_bwd_data_impl("linear_bwd_data", FORM_F32, dy, nullptr, w, residual, dx, M, N, K, relu_out, relu_scale, nullptr,
+                                nullptr, stream);
+}
+int ttts_linear_bwd_data_x6(const float* dy, const void* wt_planes, const float* residual, float* dx, int64_t M, int N, int K,
+                            const float* relu_out, float relu_scale, void* stream) {
+    return linear_bwd_data_impl("linear_bwd_data_x6", FORM_X6, dy, nullptr, wt_planes, residual, dx, M, N, K, relu_out, relu_scale,
+                                nullptr, nullptr, stream);
+}
+// dy_amax: the partial maxima of |dy| (the dynamic pre-scale of the gradient operand); dx_amax_out: NULL, or where max|dx| goes
+int ttts_linear_bwd_data_h3(const float* dy, const void* wt_planes, const float* residual, float* dx, int64_t M, int N, int K,
+                            const float* relu_out, float relu_scale, const float* dy_amax, float* dx_amax_out, void* stream) {
+    return linear_bwd_data_impl("linear_bwd_data_h3", FORM_H3, dy, nullptr, wt_planes, residual, dx, M, N, K, relu_out, relu_scale,
+                                dy_amax, dx_amax_out, stream);
+}
+int ttts_linear_bwd_data_h3i(const void* dy_image, const float* dy_row_inv, const void* wt_planes, const float* residual, float* dx,
+                             int64_t M, int N, int K, const float* relu_out, float relu_scale, float* dx_amax_out, void* stream) {
+    return linear_bwd_data_impl("linear_bwd_data_h3i", FORM_H3I, dy_image, dy_row_inv, wt_planes, residual, dx, M, N, K, relu_out,
+                                relu_scale, nullptr, dx_amax_out, stream);
+}
+int ttts_linear_bwd_data_h3d(const float* dy, const void* wt_planes, const float* residual, float* dx, int64_t M, int N, int K,
+                             const float* relu_out, float relu_scale, const float* dy_amax, float* dx_amax_out, void* stream) {
+    return linear_bwd_data_impl("linear_bwd_data_h3d", FORM_H3D, dy, nullptr, wt_planes, residual, dx, M, N, K, relu_out, relu_scale,
+                                dy_amax, dx_amax_out, stream);
+}
+
+int ttts_conv1d_fwd(const float* x, const float* w_fwd, const float* bias, float* y, int B, int T, int cin, int cout, int taps,
+                    void* stream) {
+    return conv1d_impl("conv1d_fwd", FORM_F32, true, x, w_fwd, bias, y, B, T, cin, cout, taps, nullptr, nullptr, stream);
+}
+int ttts_conv1d_fwd_x6(const float* x, const void* planes_fwd, const float* bias, float* y, int B, int T, int cin, int cout, int taps,
+                       void* stream) {
+    return conv1d_impl("conv1d_fwd_x6", FORM_X6, true, x, planes_fwd, bias, y, B, T, cin, cout, taps, nullptr, nullptr, stream);
+}
+int ttts_conv1d_fwd_h3(const float* x, const void* planes_fwd, const float* bias, float* y, int B, int T, int cin, int cout, int taps,
+                       const float* x_amax, float* bn_partials, void* stream) {
+    return conv1d_impl("conv1d_fwd_h3", FORM_H3, true, x, planes_fwd, bias, y, B, T, cin, cout, taps, x_amax, bn_partials, stream);
+}
+int ttts_conv1d_bwd_data(const float* dy, const float* w_bwd, float* dx, int B, int T, int cin, int cout, int taps, void* stream) {
+    return conv1d_impl("conv1d_bwd_data", FORM_F32, false, dy, w_bwd, nullptr, dx, B, T, cin, cout, taps, nullptr, nullptr, stream);
+}
 int ttts_conv1d_bwd_data_x6(const float* dy, const void* planes_bwd, float* dx, int B, int T, int cin, int cout, int taps,
                             void* stream) {
-    TTTS_REQUIRE(dy && planes_bwd && dx, "conv1d_bwd_data_x6: null pointer");
-    TTTS_REQUIRE(B > 0 && T > 0 && cin > 0 && cout > 0 && taps > 0 && (taps & 1), "conv1d_bwd_data_x6: bad dims");
-    TTTS_REQUIRE(cout % BK == 0, "conv1d_bwd_data_x6: cout=%d must be a multiple of %d", cout, BK);
-    TTTS_REQUIRE((uint64_t)B * T * cout * 4 < (1ull << 32), "conv1d_bwd_data_x6: activation larger than 4 GiB");
-    TTTS_REQUIRE(aligned16(dy) && aligned16(planes_bwd), "conv1d_bwd_data_x6: pointers must be 16-byte aligned");
-    GemmArgs g = base_args();
-    g.A = dy; g.B = (const float*)planes_bwd; g.C = dx; g.M = B * T; g.N = cin; g.K = taps * cout;
-    g.lda = cout; g.ldb = (long)taps * cout; g.ldc = cin;
-    g.a_bytes = (uint32_t)((uint64_t)B * T * cout * 4); g.b_bytes = (uint32_t)((uint64_t)cin * taps * cout * 6);
-    g.T = T; g.cin = cout; g.shift0 = (taps - 1) / 2; g.shift_step = -1;
-    return dispatch_split(g, (hipStream_t)stream);
+    return conv1d_impl("conv1d_bwd_data_x6", FORM_X6, false, dy, planes_bwd, nullptr, dx, B, T, cin, cout, taps, nullptr, nullptr,
+                       stream);
+}
+int ttts_conv1d_bwd_data_h3(const float* dy, const void* planes_bwd, float* dx, int B, int T, int cin, int cout, int taps,
+                            const float* dy_amax, void* stream) {
+    return conv1d_impl("conv1d_bwd_data_h3", FORM_H3, false, dy, planes_bwd, nullptr, dx, B, T, cin, cout, taps, dy_amax, nullptr,
+                       stream);
 }
 
 }  // extern "C"

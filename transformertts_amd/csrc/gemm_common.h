@@ -1,4 +1,5 @@
-// GemmArgs and the raw-buffer load helpers shared by the GEMM translation units (gemm.hip, gemm_h3.hip).
+// GemmArgs, its host-side defaults and the raw-buffer load helpers shared by the translation units that build or read a GEMM
+// problem (gemm.hip, gemm_h3.hip, gemm_h3i.hip, wgrad_dma.hip, norm.hip).
 #pragma once
 #include "ttts_common.h"
 
@@ -63,6 +64,23 @@ struct GemmArgs {
     float* c_row_inv;
     int c_amax_sec;
 };
+
+// ---- host only: the problem every entry point starts from (no shift, no split, no epilogue, no maxima), and the alignment
+// every operand the kernels read in 16-byte pieces must have
+static inline GemmArgs base_args() {
+    GemmArgs g;
+    g.A = g.B = nullptr; g.C = nullptr;
+    g.M = g.N = g.K = 0; g.lda = g.ldb = g.ldc = 0;
+    g.T = 0; g.cin = 1; g.shift0 = 0; g.shift_step = 0; g.ztaps = 1;
+    g.kt_per_split = 1 << 30; g.c_zstride = 0;
+    g.bias = nullptr; g.act = 0; g.drop_scale = 1.f; g.drop_thr = 0; g.seed = 0; g.step_seed = nullptr;
+    g.residual = nullptr; g.ldr = 0; g.colsum = nullptr; g.a_bytes = 0; g.b_bytes = 0;
+    g.relu_out = nullptr; g.relu_scale = 1.f;
+    g.a_amax = nullptr; g.a_amax_n = 0; g.b_amax = nullptr; g.b_amax_n = 0; g.c_amax = nullptr; g.bn_ws = nullptr;
+    g.a_row_inv = nullptr; g.c_row_inv = nullptr; g.c_amax_sec = 0;
+    return g;
+}
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t OOB = 0xFFFFFFFFu;

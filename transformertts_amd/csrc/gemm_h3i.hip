@@ -664,20 +664,6 @@ __global__ __launch_bounds__(256) void head_image_kernel(const float* __restrict
     }
 }
 
-static GemmArgs h3i_base_args() {
-    GemmArgs g;
-    g.A = g.B = nullptr; g.C = nullptr;
-    g.M = g.N = g.K = 0; g.lda = g.ldb = g.ldc = 0;
-    g.T = 0; g.cin = 1; g.shift0 = 0; g.shift_step = 0; g.ztaps = 1;
-    g.kt_per_split = 1 << 30; g.c_zstride = 0;
-    g.bias = nullptr; g.act = 0; g.drop_scale = 1.f; g.drop_thr = 0; g.seed = 0; g.step_seed = nullptr;
-    g.residual = nullptr; g.ldr = 0; g.colsum = nullptr; g.a_bytes = 0; g.b_bytes = 0;
-    g.relu_out = nullptr; g.relu_scale = 1.f;
-    g.a_amax = nullptr; g.a_amax_n = 0; g.b_amax = nullptr; g.b_amax_n = 0; g.c_amax = nullptr; g.bn_ws = nullptr;
-    g.a_row_inv = nullptr; g.c_row_inv = nullptr; g.c_amax_sec = 0;
-    return g;
-}
-
 }  // namespace ttts
 
 using namespace ttts;
@@ -693,12 +679,10 @@ extern "C" int ttts_dbg_h3i_read_stamps(unsigned long long* host, size_t n) {
 }
 #endif
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 extern "C" int ttts_act_image(const float* x, void* image, float* row_inv, int64_t M, int K, void* stream) {
     TTTS_REQUIRE(x && image && row_inv, "act_image: null pointer");
     TTTS_REQUIRE(M > 0 && K > 0 && K % 16 == 0 && K <= 1024, "act_image: K=%d must be a multiple of 16, at most 1024", K);
-    TTTS_REQUIRE(al16(x) && al16(image), "act_image: pointers must be 16-byte aligned");
+    TTTS_REQUIRE(aligned16(x) && aligned16(image), "act_image: pointers must be 16-byte aligned");
     const dim3 grid((unsigned)cdiv(M, 4));
     if (K <= 256) hipLaunchKernelGGL((act_image_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)image, row_inv, (long)M, K);
     else if (K <= 512) hipLaunchKernelGGL((act_image_kernel<2>), grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)image, row_inv, (long)M, K);
@@ -707,132 +691,13 @@ extern "C" int ttts_act_image(const float* x, void* image, float* row_inv, int64
     return TTTS_OK;
 }
 
-extern "C" int ttts_linear_fwd_h3i(const void* x_image, const float* x_row_inv, const void* w_planes, const float* bias,
-                                   const float* residual, float* y, int64_t M, int N, int K, int act, float drop_p, uint64_t seed,
-                                   const uint64_t* step_seed, float* y_amax_out, void* stream) {
-    TTTS_REQUIRE(x_image && x_row_inv && w_planes && y, "linear_fwd_h3i: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_fwd_h3i: bad dims");
-    TTTS_REQUIRE(K % 32 == 0 && N % 4 == 0, "linear_fwd_h3i: K=%d must be a multiple of 32 and N=%d of 4", K, N);
-    TTTS_REQUIRE(al16(x_image) && al16(w_planes) && al16(y), "linear_fwd_h3i: pointers must be 16-byte aligned");
-    TTTS_REQUIRE(act == 0 || act == 1, "linear_fwd_h3i: act must be 0 (none) or 1 (relu)");
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "linear_fwd_h3i: dropout p out of [0,1)");
-    TTTS_REQUIRE((uint64_t)M * K * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_fwd_h3i: operand larger than 4 GiB");
-    GemmArgs g = h3i_base_args();
-    g.A = (const float*)x_image; g.B = (const float*)w_planes; g.C = y; g.M = (int)M; g.N = N; g.K = K;
-    g.lda = K; g.ldb = K; g.ldc = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * K * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.cin = K;
-    g.bias = bias; g.act = act;
-    if (drop_p > 0.f) { g.drop_thr = drop_threshold(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.seed = seed; g.step_seed = step_seed; }
-    g.residual = residual; g.ldr = N;
-    g.a_row_inv = x_row_inv;
-    g.b_amax = h3_plane_tail(w_planes, N, K); g.b_amax_n = 1;
-    g.c_amax = y_amax_out;
-    return dispatch_h3i(g, (hipStream_t)stream);
-}
-
-extern "C" int ttts_linear_bwd_data_h3i(const void* dy_image, const float* dy_row_inv, const void* wt_planes, const float* residual,
-                                        float* dx, int64_t M, int N, int K, const float* relu_out, float relu_scale,
-                                        float* dx_amax_out, void* stream) {
-    // dx[M,K] = dy[M,N] . w[N,K] (+ residual): the gradient is the image operand; wt_planes = weight_split mode 5 (w^T)
-    TTTS_REQUIRE(dy_image && dy_row_inv && wt_planes && dx, "linear_bwd_data_h3i: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_bwd_data_h3i: bad dims");
-    TTTS_REQUIRE(N % 32 == 0 && K % 4 == 0, "linear_bwd_data_h3i: N=%d must be a multiple of 32 and K=%d of 4", N, K);
-    TTTS_REQUIRE(al16(dy_image) && al16(wt_planes) && al16(dx), "linear_bwd_data_h3i: pointers must be 16-byte aligned");
-    TTTS_REQUIRE((uint64_t)M * N * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_bwd_data_h3i: operand larger than 4 GiB");
-    GemmArgs g = h3i_base_args();
-    g.A = (const float*)dy_image; g.B = (const float*)wt_planes; g.C = dx; g.M = (int)M; g.N = K; g.K = N;
-    g.lda = N; g.ldb = N; g.ldc = K; g.cin = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * N * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.residual = residual; g.ldr = K;
-    g.relu_out = relu_out; g.relu_scale = relu_scale;
-    g.a_row_inv = dy_row_inv;
-    g.b_amax = h3_plane_tail(wt_planes, K, N); g.b_amax_n = 1;
-    g.c_amax = dx_amax_out;
-    return dispatch_h3i(g, (hipStream_t)stream);
-}
-
-/* fp32 activation (per-tensor scale from its partial maxima) on the LDS-DMA kernel: the weight image is the K16-major one
- * (ttts_weight_split modes 8 / 9); arguments otherwise as ttts_linear_fwd_h3 / ttts_linear_bwd_data_h3 without a row shift */
-extern "C" int ttts_linear_fwd_h3d(const float* x, const void* w_planes, const float* bias, const float* residual, float* y,
-                                   int64_t M, int N, int K, int act, float drop_p, uint64_t seed, const uint64_t* step_seed,
-                                   const float* x_amax, float* y_amax_out, void* stream) {
-    TTTS_REQUIRE(x && w_planes && y && x_amax, "linear_fwd_h3d: null pointer (x_amax, the partial maxima of |x|, is required)");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_fwd_h3d: bad dims");
-    TTTS_REQUIRE(K % 32 == 0 && N % 4 == 0, "linear_fwd_h3d: K=%d must be a multiple of 32 and N=%d of 4", K, N);
-    TTTS_REQUIRE(al16(x) && al16(w_planes) && al16(y), "linear_fwd_h3d: pointers must be 16-byte aligned");
-    TTTS_REQUIRE(act == 0 || act == 1, "linear_fwd_h3d: act must be 0 (none) or 1 (relu)");
-    TTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "linear_fwd_h3d: dropout p out of [0,1)");
-    TTTS_REQUIRE((uint64_t)M * K * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_fwd_h3d: operand larger than 4 GiB");
-    GemmArgs g = h3i_base_args();
-    g.A = x; g.B = (const float*)w_planes; g.C = y; g.M = (int)M; g.N = N; g.K = K;
-    g.lda = K; g.ldb = K; g.ldc = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * K * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.cin = K;
-    g.bias = bias; g.act = act;
-    if (drop_p > 0.f) { g.drop_thr = drop_threshold(drop_p); g.drop_scale = 1.f / (1.f - drop_p); g.seed = seed; g.step_seed = step_seed; }
-    g.residual = residual; g.ldr = N;
-    g.a_amax = x_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(w_planes, N, K); g.b_amax_n = 1;
-    g.c_amax = y_amax_out;
-    return dispatch_h3i(g, (hipStream_t)stream);
-}
-
-extern "C" int ttts_linear_bwd_data_h3d(const float* dy, const void* wt_planes, const float* residual, float* dx, int64_t M, int N,
-                                        int K, const float* relu_out, float relu_scale, const float* dy_amax, float* dx_amax_out,
-                                        void* stream) {
-    TTTS_REQUIRE(dy && wt_planes && dx && dy_amax, "linear_bwd_data_h3d: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_bwd_data_h3d: bad dims");
-    TTTS_REQUIRE(N % 32 == 0 && K % 4 == 0, "linear_bwd_data_h3d: N=%d must be a multiple of 32 and K=%d of 4", N, K);
-    TTTS_REQUIRE(al16(dy) && al16(wt_planes) && al16(dx), "linear_bwd_data_h3d: pointers must be 16-byte aligned");
-    TTTS_REQUIRE((uint64_t)M * N * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_bwd_data_h3d: operand larger than 4 GiB");
-    GemmArgs g = h3i_base_args();
-    g.A = dy; g.B = (const float*)wt_planes; g.C = dx; g.M = (int)M; g.N = K; g.K = N;
-    g.lda = N; g.ldb = N; g.ldc = K; g.cin = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * N * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.residual = residual; g.ldr = K;
-    g.relu_out = relu_out; g.relu_scale = relu_scale;
-    g.a_amax = dy_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(wt_planes, K, N); g.b_amax_n = 1;
-    g.c_amax = dx_amax_out;
-    return dispatch_h3i(g, (hipStream_t)stream);
-}
-
-/* The in-projections of nn.MultiheadAttention (packed q/k/v, or its q and k/v row slices: torch/nn/functional.py:6206+ reached
- * from model/layers.py:54-74 and torch _sa_block) with a HEAD-IMAGE output: y_image has the geometry of the fp32 output (M rows of
- * N 4-byte cells) but holds, per row and 64-column head, {64 f16 hi, 64 f16 lo} of (x W^T + b) * 2^e(row, head);
- * y_row_inv[head * M + row] = 2^-e.  y_amax_out: NULL, or N / amax_section_cols caller-zeroed TTTS_AMAX_SLOTS-float arrays (one per
- * section: q / k / v), each receiving max|y| of its section. */
-extern "C" int ttts_linear_fwd_h3d_img(const float* x, const void* w_planes, const float* bias, void* y_image, float* y_row_inv,
-                                       int64_t M, int N, int K, const float* x_amax, float* y_amax_out, int amax_section_cols,
-                                       void* stream) {
-    TTTS_REQUIRE(x && w_planes && y_image && y_row_inv && x_amax, "linear_fwd_h3d_img: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_fwd_h3d_img: bad dims");
-    TTTS_REQUIRE(K % 32 == 0 && N % 64 == 0, "linear_fwd_h3d_img: K=%d must be a multiple of 32 and N=%d of 64", K, N);
-    TTTS_REQUIRE(al16(x) && al16(w_planes) && al16(y_image), "linear_fwd_h3d_img: pointers must be 16-byte aligned");
-    TTTS_REQUIRE(amax_section_cols >= 0 && (amax_section_cols == 0 || (amax_section_cols % 64 == 0 && N % amax_section_cols == 0)),
-                 "linear_fwd_h3d_img: amax sections must be whole heads that divide N");
-    TTTS_REQUIRE((uint64_t)M * K * 4 < (1ull << 32) && (uint64_t)N * K * 4 < (1ull << 32), "linear_fwd_h3d_img: operand larger than 4 GiB");
-    GemmArgs g = h3i_base_args();
-    g.A = x; g.B = (const float*)w_planes; g.C = (float*)y_image; g.M = (int)M; g.N = N; g.K = K;
-    g.lda = K; g.ldb = K; g.ldc = N;
-    g.a_bytes = (uint32_t)((uint64_t)M * K * 4); g.b_bytes = (uint32_t)((uint64_t)N * K * 4);
-    g.cin = K;
-    g.bias = bias;
-    g.a_amax = x_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-    g.b_amax = h3_plane_tail(w_planes, N, K); g.b_amax_n = 1;
-    g.c_amax = y_amax_out; g.c_amax_sec = amax_section_cols;
-    g.c_row_inv = y_row_inv;
-    return dispatch_h3i(g, (hipStream_t)stream);
-}
-
 /* fp32 rows (row stride ld_x floats) -> head image (row stride ld_image 4-byte cells) + inverse scales [N / 64][M] */
 extern "C" int ttts_head_image(const float* x, int64_t ld_x, void* image, int64_t ld_image, float* row_inv, int64_t M, int N,
                                void* stream) {
     TTTS_REQUIRE(x && image && row_inv, "head_image: null pointer");
     TTTS_REQUIRE(M > 0 && N > 0 && N % 64 == 0 && ld_x >= N && ld_image >= N && ld_x % 4 == 0 && ld_image % 4 == 0,
                  "head_image: N=%d must be a multiple of 64 and the row strides multiples of 4 that cover it", N);
-    TTTS_REQUIRE(al16(x) && al16(image), "head_image: pointers must be 16-byte aligned");
+    TTTS_REQUIRE(aligned16(x) && aligned16(image), "head_image: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(head_image_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, (long)ld_x,
                        (unsigned short*)image, (long)ld_image, row_inv, (long)M, N);
     TTTS_LAUNCH_CHECK("head_image_kernel");

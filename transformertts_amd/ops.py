@@ -797,6 +797,10 @@ IMAGE_MIN_ROWS = 8192
 # LayerNorm leaves images only when asked (tests, `layer_norm(..., emit_image=True)`); what the step uses by default is the same
 # kernel on the plain fp32 operand (`_dma_shape_ok`), where it needs no producer and still wins.
 LAYERNORM_IMAGES = False
+# Plain fp32 activations on the LDS-DMA kernel (ttts_linear_*_h3d) on the shapes where it beats gemm_h3 (`_dma_shape_ok`)
+DMA_GEMMS = True
+DMA_BIG_FWD = True          # 256 -> 1024 forward GEMMs (FFN1) on the 256-row LDS-DMA tile when its tiles fill the chip (tools/h3i_bench.py)
+DMA_MIN_TILES = 320         # square projections take the LDS-DMA kernel from this many 128 x 256 tiles on (326 tiles: 1.04x, `_dma_shape_ok`)
 
 
 def _image_rows_ok(M: int, d: int) -> bool:
@@ -826,9 +830,6 @@ def _dma_shape_ok(M: int, red: int, out: int, gate: bool) -> bool:
     return red == out and out in (256, 512) and -(-M // 128) * -(-out // 256) >= DMA_MIN_TILES
 
 
-DMA_MIN_TILES = 320
-
-
 def _dma_dims(red: int, out: int) -> bool:
     """could `_dma_shape_ok` say yes for SOME row count?  The choice between the two kernels (and so between the two weight
     images, H3_LIN_FWD / H3D_LIN_FWD resp. H3_LIN_BWD / H3D_LIN_BWD) depends on the batch's row count, and a captured graph can
@@ -844,12 +845,10 @@ def _image_dims(red: int, out: int) -> bool:
 
 
 def _both_images(w: torch.Tensor, used: int, other: int, rows: int, cols: int) -> torch.Tensor:
-    """planes of `w` in mode `used`; outside a capture also make sure its sibling image (`other`) exists"""
-    if not torch.cuda.is_current_stream_capturing():
+    """planes of `w` in mode `used`; outside a capture also make sure its sibling image (`other`, when there is one) exists"""
+    if other is not None and not torch.cuda.is_current_stream_capturing():
         _planes(w, other, rows, cols)
     return _planes(w, used, rows, cols)
-DMA_GEMMS = True
-DMA_BIG_FWD = True          # 256 -> 1024 forward GEMMs (FFN1) on the 256-row LDS-DMA tile when its tiles fill the chip (tools/h3i_bench.py)
 
 
 def _new_image(M: int, d: int, device):
@@ -859,34 +858,51 @@ def _new_image(M: int, d: int, device):
 _BIAS_ONLY = (ACT_NONE, 0.0, 0, None, 0, 0)
 
 
+def _linear_route(fwd: bool, M: int, red: int, out: int, *, operand_image: bool = False, shifted: bool = False, gate: bool = False,
+                  skip: bool = False, tiles: bool = True, w_image: bool = False):
+    """The one decision of `_linear_fwd` (fwd) / `_linear_bwd_data`: which kernel family runs M rows of reduction depth `red`
+    and output width `out`, and on which weight image.
+      operand_image  the activation's producer left an image of it;  shifted: the forward reads its rows shifted
+      gate / skip    the data gradient applies a relu gate / adds a skip gradient
+      tiles          False: no kernel choice (the mel head);  w_image: the data gradient was handed a ready weight image
+    -> (family, mode, sibling): "x6" (the shape fallback), "h3i" (image operand), "h3d" (LDS-DMA) or "h3" (gemm_h3); the
+    `_planes` mode of the weight image it reads (None: the caller's `w_image`); the mode `_both_images` makes first outside a
+    capture, or None.  No tensor work, no library call.  Kept as the two ladders had them, not judged here:
+      - the data gradient takes an operand image only when `_image_shape_ok`; the forward trusts whoever left the image;
+      - the data gradient keeps gate plus skip off the LDS-DMA kernel;
+      - a shifted forward is a `tiles=False` call: gemm_h3 and no sibling image, whatever the shape."""
+    base = 0 if fwd else 1                             # the modes come in (forward, data gradient) pairs
+    if not w_image and not _h3_shape_ok(red, out):
+        return "x6", X6_LIN_FWD + base, None
+    tiles = tiles and not shifted and not w_image      # (the LDS-DMA kernels have no shifted loader)
+    h3, h3d = H3_LIN_FWD + base, H3D_LIN_FWD + base
+    if operand_image and tiles and (fwd or _image_shape_ok(M, red, out)):
+        return "h3i", h3d, h3
+    both = tiles and (_dma_dims(red, out) or _image_dims(red, out))
+    if tiles and _dma_shape_ok(M, red, out, gate) and not (gate and skip):
+        return "h3d", h3d, h3 if both else None
+    return "h3", None if w_image else h3, h3d if both else None
+
+
 def _linear_fwd(x, w, b, r, y, M: int, N: int, K: int, x_amax, y_amax, epi=_BIAS_ONLY, x_image=None, tiles: bool = True):
     """Launch y = drop(act(x w^T + b)) + r over M rows; -> the partial maxima of x it used (or None).
     epi = (act, drop_p, seed, step_seed, row_shift, T); x_amax: None = measured here; y_amax: None, or where max|y| goes;
     x_image: (image, row_inv) of x left by its producer -- the image-operand kernel.  `tiles=False`: no kernel choice here --
     gemm_h3 on the H3_LIN_FWD image whatever the row count, and no sibling image is made (the mel head)."""
     lib = _lib.load()
-    if not _h3_shape_ok(K, N):
-        # the shape fallback: K or N no multiple of 4 -- the only launches of ops that are not fp16x3 (with their data
-        # gradient, _linear_bwd_data, and ConvBNFn's two)
-        _lib.check(lib.ttts_linear_fwd_x6(_p(x), _p(_planes(w, X6_LIN_FWD, N, K)), _p(b), _p(r), _p(y), M, N, K, *epi, _stream()),
-                   "ttts_linear_fwd_x6")
-        return x_amax
-    tiles = tiles and epi[4] == 0                      # (the LDS-DMA kernels have no shifted loader)
-    if x_image is not None and tiles:
-        _lib.check(lib.ttts_linear_fwd_h3i(_p(x_image[0]), _p(x_image[1]), _p(_both_images(w, H3D_LIN_FWD, H3_LIN_FWD, N, K)), _p(b),
-                                           _p(r), _p(y), M, N, K, *epi[:4], _p(y_amax), _stream()), "ttts_linear_fwd_h3i")
-        return x_amax
-    if x_amax is None:
+    kind, mode, sibling = _linear_route(True, M, K, N, operand_image=x_image is not None, shifted=epi[4] != 0, tiles=tiles)
+    if x_amax is None and kind in ("h3d", "h3"):
         x_amax = _amax(x)
-    both = tiles and (_dma_dims(K, N) or _image_dims(K, N))
-    if tiles and _dma_shape_ok(M, K, N, False):
-        planes = _both_images(w, H3D_LIN_FWD, H3_LIN_FWD, N, K) if both else _planes(w, H3D_LIN_FWD, N, K)
-        _lib.check(lib.ttts_linear_fwd_h3d(_p(x), _p(planes), _p(b), _p(r), _p(y), M, N, K, *epi[:4], _p(x_amax), _p(y_amax),
-                                           _stream()), "ttts_linear_fwd_h3d")
+    planes = _p(_both_images(w, mode, sibling, N, K))
+    if kind == "x6":        # K or N no multiple of 4 -- with its data gradient and ConvBNFn's two the only launches that are not fp16x3
+        rc = lib.ttts_linear_fwd_x6(_p(x), planes, _p(b), _p(r), _p(y), M, N, K, *epi, _stream())
+    elif kind == "h3i":
+        rc = lib.ttts_linear_fwd_h3i(_p(x_image[0]), _p(x_image[1]), planes, _p(b), _p(r), _p(y), M, N, K, *epi[:4], _p(y_amax), _stream())
+    elif kind == "h3d":
+        rc = lib.ttts_linear_fwd_h3d(_p(x), planes, _p(b), _p(r), _p(y), M, N, K, *epi[:4], _p(x_amax), _p(y_amax), _stream())
     else:
-        planes = _both_images(w, H3_LIN_FWD, H3D_LIN_FWD, N, K) if both else _planes(w, H3_LIN_FWD, N, K)
-        _lib.check(lib.ttts_linear_fwd_h3(_p(x), _p(planes), _p(b), _p(r), _p(y), M, N, K, *epi, _p(x_amax), _p(y_amax), _stream()),
-                   "ttts_linear_fwd_h3")
+        rc = lib.ttts_linear_fwd_h3(_p(x), planes, _p(b), _p(r), _p(y), M, N, K, *epi, _p(x_amax), _p(y_amax), _stream())
+    _lib.check(rc, "ttts_linear_fwd_" + kind)
     return x_amax
 
 
@@ -899,28 +915,21 @@ def _linear_bwd_data(dy, w, dx, M: int, N: int, K: int, dy_amax, skip=None, gate
     not read and may be None."""
     lib = _lib.load()
     assert w is not None or w_image is not None
-    if w_image is None and not _h3_shape_ok(N, K):                  # the shape fallback (see _linear_fwd)
-        _lib.check(lib.ttts_linear_bwd_data_x6(_p(dy), _p(_planes(w, X6_LIN_BWD, K, N)), _p(skip), _p(dx), M, N, K, _p(gate), gscale,
-                                               _stream()), "ttts_linear_bwd_data_x6")
-        return dy_amax
-    tiles = tiles and w_image is None
-    if dy_image is not None and tiles and _image_shape_ok(M, N, K):
-        _lib.check(lib.ttts_linear_bwd_data_h3i(_p(dy_image[0]), _p(dy_image[1]), _p(_both_images(w, H3D_LIN_BWD, H3_LIN_BWD, K, N)),
-                                                _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dx_amax), _stream()),
-                   "ttts_linear_bwd_data_h3i")
-        return dy_amax
-    if dy_amax is None:
+    kind, mode, sibling = _linear_route(False, M, N, K, operand_image=dy_image is not None, gate=gate is not None,
+                                        skip=skip is not None, tiles=tiles, w_image=w_image is not None)
+    if dy_amax is None and kind in ("h3d", "h3"):
         dy_amax = _amax(dy)
-    both = tiles and (_dma_dims(N, K) or _image_dims(N, K))
-    if tiles and _dma_shape_ok(M, N, K, gate is not None) and not (gate is not None and skip is not None):
-        planes = _both_images(w, H3D_LIN_BWD, H3_LIN_BWD, K, N) if both else _planes(w, H3D_LIN_BWD, K, N)
-        _lib.check(lib.ttts_linear_bwd_data_h3d(_p(dy), _p(planes), _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dy_amax),
-                                                _p(dx_amax), _stream()), "ttts_linear_bwd_data_h3d")
+    planes = _p(w_image if mode is None else _both_images(w, mode, sibling, K, N))
+    if kind == "x6":        # the shape fallback (see _linear_fwd)
+        rc = lib.ttts_linear_bwd_data_x6(_p(dy), planes, _p(skip), _p(dx), M, N, K, _p(gate), gscale, _stream())
+    elif kind == "h3i":
+        rc = lib.ttts_linear_bwd_data_h3i(_p(dy_image[0]), _p(dy_image[1]), planes, _p(skip), _p(dx), M, N, K, _p(gate), gscale,
+                                          _p(dx_amax), _stream())
+    elif kind == "h3d":
+        rc = lib.ttts_linear_bwd_data_h3d(_p(dy), planes, _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dy_amax), _p(dx_amax), _stream())
     else:
-        if w_image is None:
-            w_image = _both_images(w, H3_LIN_BWD, H3D_LIN_BWD, K, N) if both else _planes(w, H3_LIN_BWD, K, N)
-        _lib.check(lib.ttts_linear_bwd_data_h3(_p(dy), _p(w_image), _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dy_amax),
-                                               _p(dx_amax), _stream()), "ttts_linear_bwd_data_h3")
+        rc = lib.ttts_linear_bwd_data_h3(_p(dy), planes, _p(skip), _p(dx), M, N, K, _p(gate), gscale, _p(dy_amax), _p(dx_amax), _stream())
+    _lib.check(rc, "ttts_linear_bwd_data_" + kind)
     return dy_amax
 
 
