@@ -124,7 +124,9 @@ int ttts_linear_bwd_data(const float* dy, const float* w, const float* residual,
                          const float* relu_out, float relu_scale, void* stream);
 /* dw[N,K] = dy[M,N]^T . x[M,K] (x rows shifted as in forward); dbias[N] = column sums of dy (optional).
  * Every parameter-gradient output in this header takes `accumulate`: 0 stores, 1 adds to what is there, so that
- * gradients can land directly in slices of one flat, pre-zeroed gradient buffer (the data-parallel bucket). */
+ * gradients can land directly in slices of one flat, pre-zeroed gradient buffer (the data-parallel bucket).
+ * ttts_wgrad_workspace_bytes: the workspace of the problem in every form (fp32, _x6, _h3, _h3_parts; taps > 1: the Conv1d entries
+ * with M = B T, N = cout, K = cin) and as a member of any ttts_wgrad_group; 0 for a dimension that is not positive. */
 size_t ttts_wgrad_workspace_bytes(int64_t M, int N, int K, int taps);
 int ttts_linear_bwd_weight(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes,
                            int64_t M, int N, int K, int row_shift, int T, int accumulate, ttts_reduce_queue* queue,
@@ -278,8 +280,9 @@ int ttts_conv1d_bwd_weight_h3(const float* dy, const float* x, float* dw, float*
  * T); taps_i > 1: the weight gradient
  * of a same-padded convolution over utterances of T_i rows, dw_i[N_i = cout, K_i = cin, taps_i], M_i = B T_i
  * (ttts_conv1d_bwd_weight_h3).  dbias_i: column sums of dy_i, or NULL.  Every array argument is a HOST array of n entries; ws_i /
- * ws_bytes_i as ttts_wgrad_workspace_bytes(M_i, N_i, K_i, taps_i).  The row splits are planned for the group, so each member writes
- * 1/n of the partial sums of a launch of its own.  ttts_wgrad_group_ok: the CLASS of a problem -- 0: no member of any group; 1: the
+ * ws_bytes_i as ttts_wgrad_workspace_bytes(M_i, N_i, K_i, taps_i), which covers the member in any group (alone too, where an output
+ * of one tile is planned more row splits than in a launch of its own).  The row splits are planned for the group, so each member of
+ * n writes 1/n of the partial sums of a launch of its own.  ttts_wgrad_group_ok: the CLASS of a problem -- 0: no member of any group; 1: the
  * 4-wave 128 x 128 tile; 2: whole 256 x 256 tiles on the 8-wave LDS-DMA kernel (the FFN, packed in-projection and post-net
  * convolution weights over long row ranges); 3 / 4: the 128 x 96 / 96 x 128 tiles of weights with 80 input / output channels
  * (the mel side) -- the members of one launch share a class.  (The autograd of torch.nn.Linear /

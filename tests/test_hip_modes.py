@@ -349,6 +349,39 @@ def test_grouped_weight_gradients(M, shapes):
     assert all(torch.equal(a, b) for a, b in zip(first, dws2))
 
 
+@pytest.fixture(scope="module")
+def _one_tile_operands():
+    """dy (50 000 x 128), x (50 000 x 128) and their fp64 product, shared by the five lone members below"""
+    M = 50000
+    dy, x = _rand(M, 128, seed=61) * 1e-2, _rand(M, 128, seed=62)
+    return M, dy, x, dy.double().t() @ x.double(), dy.double().sum(0)
+
+
+@pytest.mark.parametrize("N,K,bias", [(128, 128, True), (80, 128, False), (96, 128, True), (128, 80, False), (128, 96, False)])
+def test_a_lone_one_tile_member_of_a_grouped_launch(_one_tile_operands, N, K, bias):
+    """An output of ONE tile, alone in ttts_wgrad_group, over 50 000 rows: the group plans 196 row splits of 8 k-tiles, more than any
+    launch of its own (at most 192), and ttts_wgrad_workspace_bytes has to cover them -- from this row count on it did not, and
+    the group refused the workspace its header told the caller to allocate.  Against fp64, the bound of every other split count."""
+    import ctypes
+    from transformertts_amd import _lib, ops
+    from transformertts_amd.ops import _stream
+    lib, dev = _lib.load(), _dev()
+    M, dy_all, x_all, dw_ref, db_ref = _one_tile_operands
+    dy, x = dy_all[:, :N].contiguous(), x_all[:, :K].contiguous()
+    assert lib.ttts_wgrad_group_ok(M, N, K, 1) == (4 if N < 128 else 3 if K < 128 else 1)
+    ws = torch.empty(lib.ttts_wgrad_workspace_bytes(M, N, K, 1) // 4, device=dev)
+    assert ws.numel() >= 196 * (N * K + N)
+    dw, db = torch.zeros(N, K, device=dev), torch.zeros(N, device=dev) if bias else None
+    am, xm = ops._amax(dy), ops._amax(x)
+    P, Z, L, I = ctypes.c_void_p * 1, ctypes.c_size_t * 1, ctypes.c_int64 * 1, ctypes.c_int * 1
+    rc = lib.ttts_wgrad_group(1, P(dy.data_ptr()), P(x.data_ptr()), P(dw.data_ptr()), P(db.data_ptr() if bias else None), P(ws.data_ptr()),
+                              Z(ws.numel() * 4), L(M), I(N), I(K), I(1), I(0), I(0), 1, P(am.data_ptr()), P(xm.data_ptr()), None, _stream())
+    assert rc == 0, _lib.last_error()
+    err = _rel(dw, dw_ref[:N, :K])
+    print(f"lone member {N}x{K} over {M} rows: dw {err:.2e}" + (f" db {_rel(db, db_ref[:N]):.2e}" if bias else ""))
+    assert err < TOL and (not bias or _rel(db, db_ref[:N]) < TOL)
+
+
 @pytest.mark.parametrize("B,T,chans", [(64, 100, [(256, 256), (256, 256), (256, 256)]),       # the encoder pre-net's convolutions
                                        (30, 870, [(256, 256), (256, 256), (256, 256)]),        # the post-net's: the LDS-DMA tile, 5 taps each
                                        (7, 33, [(256, 128), (128, 256)])])

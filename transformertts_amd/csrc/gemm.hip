@@ -963,47 +963,64 @@ static int dispatch_wgrad_split(const GemmArgs& g, int zdim, int tile, hipStream
     }
 }
 
-// how the row (reduction) dimension of a weight gradient is split.  The fp32-MFMA / bf16x6 kernels aim at about 768
+// ---------------------------------------------------------------------------------------------------------------
+// Weight gradients: the problem C[N][K] (per tap) = dy^T[N][M] . x_shifted[M][K] with the row (reduction) dimension split over the
+// grid's z, and a second stage that sums the partial products.  One planner, one description of the problem, one workspace layout,
+// one set of checks and one body per stage serve all ten entry points.
+enum WgradForm { WG_F32, WG_X6, WG_H3 };        // fp32 MFMA, bf16x6 (16-row k-steps), fp16x3 (32-row k-steps, dynamic pre-scales)
+struct WgradPlan { int tile; int nsplit; int kt_per_split; long tiles; };
+// a grouped launch as its members' plans see it: the class (ttts_wgrad_group_ok), the tile total, the longest row range in k-tiles
+struct WgradGroup { int cls; long tiles_total; long nkt_max; };
+
+// The workgroups a launch OF ITS OWN aims at.  The fp32-MFMA / bf16x6 kernels aim at about 768
 // workgroups (3 per CU).  The fp16x3 kernel holds two workgroups per CU, so 768 is one full round plus a half-empty one;
 // it gets ONE round -- 512 workgroups for outputs of more than 12 tiles over long row ranges, else 256: every split costs
 // a partial tile written and read again, which for the small outputs weighs more than a second workgroup per CU brings
 // (measured on the step's shapes, tools/wgrad_bench.py: 256x256 118 -> 134, 768x256 157 -> 188, 256x1024 189 -> 214 TF).
-struct WgradPlan { int tile; int nsplit; int kt_per_split; };
-static WgradPlan plan_wgrad(int64_t M, int N, int K, int taps, bool x6 = false, int bk = BK) {
-    WgradPlan p;
-    long tiles = (long)cdiv(N, 128) * cdiv(K, 128) * taps;
+static long wgrad_target_single(WgradForm f, int tile, long tiles, long nkt) {
+    if (f != WG_H3) return 768;
+    if (tile == H3_TILE_256) return 256;                           // (the 8-wave tile holds one workgroup per CU)
+    return (tiles > 12 && nkt >= 800) ? 512 : 256;
+}
+
+// The workgroups a GROUPED launch aims at -- the rule above applied to the group as a whole: the 8-wave tile (class 2) holds one
+// workgroup per CU, the 4-wave tile two (a second round only for many tiles over long row ranges)
+// (the 96-wide tiles' workgroups are long -- 10 + 2 tiles of the mel side over 55 680 rows were 140 us on 252 workgroups -- and
+// their partial tiles small: both workgroup slots of every CU from 8 tiles on)
+// (row ranges from 200 k-tiles on -- 6 400 rows: at 13 920 rows a group on ONE workgroup slot per CU ran its 109 k-tiles per
+// workgroup at a fifth of the MFMA rate, nothing covering its operand latencies: batch 16 -0.08 ms, `profiles/r06_ab_wgrad_target.txt`)
+constexpr long WG_GROUP_NKT512 = 200;
+static long wgrad_group_many(int cls) { return (cls == 3 || cls == 4) ? 8 : 13; }
+static long wgrad_target_group(const WgradGroup& grp) {
+    if (grp.cls == 2) return 256;
+    return (grp.tiles_total >= wgrad_group_many(grp.cls) && grp.nkt_max >= WG_GROUP_NKT512) ? 512 : 256;
+}
+
+// THE planner: the tile of dw[N][K] x taps over M rows in form `f`, and how the rows are split -- for a launch of its own, or
+// (grp) as a member of a grouped launch, whose workgroup target is shared by the tiles of all members.  M, N, K, taps > 0.
+static WgradPlan plan_wgrad(int64_t M, int N, int K, int taps, WgradForm f, const WgradGroup* grp = nullptr) {
+    WgradPlan p; const long bk = f == WG_H3 ? HBK : BK, nkt = (M + bk - 1) / bk;
     p.tile = (K <= 96) ? TILE_128x96 : TILE_128;
-    long nkt = (M + bk - 1) / bk;
-    if (x6) {
+    p.tiles = (long)cdiv(N, 128) * cdiv(K, 128) * taps;
+    if (f != WG_F32) {
         // the split-precision kernel wants the large tile (its per-thread staging work is fixed per k-step); small
         // outputs get more row splits instead, capped so that the partial sums stay a few tens of MB
-        if (N <= 64 && K <= 64) { p.tile = TILE_64; tiles = (long)cdiv(N, 64) * cdiv(K, 64) * taps; }
+        if (N <= 64 && K <= 64) { p.tile = TILE_64; p.tiles = (long)cdiv(N, 64) * cdiv(K, 64) * taps; }
         else if (N <= 96 && K > 96) p.tile = TILE_96x128;          // 80-wide mel outputs
-    } else if (tiles < 16) {
-        p.tile = TILE_64; tiles = (long)cdiv(N, 64) * cdiv(K, 64) * taps;
-    }
-    constexpr long forced = 0;
-    constexpr int big = 1;
-    long target = 768;
-    if (bk == HBK) {
+    } else if (p.tiles < 16) { p.tile = TILE_64; p.tiles = (long)cdiv(N, 64) * cdiv(K, 64) * taps; }
+    if (f == WG_H3) {
         // The kernel's speed is set by the operand bytes its workgroups request (tiles x rows x (BM + BN) x 4 B at about
         // 7.7 TB/s over the chip: 1024x256 with 128-wide tiles asks for 913 MB = 119 us, measured 119), so outputs of three
         // or more 256 x 256 tiles take the 8-wave 256-wide tile (half the bytes per product) on one workgroup per CU.  Smaller
         // outputs stay on the 128-wide tile: at 256 row splits their partial sums (256 KB each, written and read back)
         // would cost what the operands save.
         const long tiles256 = (long)cdiv(N, 256) * cdiv(K, 256) * taps;
-        if (big && p.tile == TILE_128 && N >= 256 && K >= 256 && tiles256 >= 3 && nkt >= 800) {
-            p.tile = H3_TILE_256;
-            tiles = tiles256;
-            target = 256;
-        } else {
-            target = (tiles > 12 && nkt >= 800) ? 512 : 256;
-        }
+        if (p.tile == TILE_128 && N >= 256 && K >= 256 && tiles256 >= 3 && nkt >= 800) { p.tile = H3_TILE_256; p.tiles = tiles256; }
     }
-    if (forced > 0) target = forced;
-    long want = target / tiles;
+    // the row splits: `want` per tile, at most one per k-tile, at least 8 k-tiles each
+    long want = grp ? wgrad_target_group(*grp) / grp->tiles_total : wgrad_target_single(f, p.tile, p.tiles, nkt) / p.tiles;
     if (want < 1) want = 1;
-    if (x6 && want > 128) want = 128;
+    if (!grp && f != WG_F32 && want > 128) want = 128;             // (the cap on a small output's partial sums, above)
     if (want > nkt) want = nkt;
     long per = (nkt + want - 1) / want;
     if (per < 8 && nkt >= 8) per = 8;
@@ -1016,6 +1033,120 @@ static WgradPlan plan_wgrad(int64_t M, int N, int K, int taps, bool x6 = false, 
 // are reasonably full
 static bool wgrad_use_x6(int N, int K) { return (N >= 128 || N == 80 || N == 96) && (K >= 128 || K == 80 || K == 96) && (N >= 128 || K >= 128); }
 
+// can dw[N,K(,tap)] = dy[M,N]^T x[M(+tap shift),K] be a member of a grouped launch, and of which CLASS (members of one launch
+// share it)?  1: the fp16x3 form on the 4-wave 128 x 128 tile (small outputs); 2: whole 256 x 256 tiles on the 8-wave LDS-DMA
+// kernel (long row ranges); 3 / 4: the 96-wide tiles of the 80-channel mel side; 0: none (the fp32-MFMA shapes, ragged
+// 256-tiles keep launches of their own).  taps = 1: a linear weight; taps > 1: a convolution's (cout = N, cin = K).  The class's
+// tile is the one of the problem's own fp16x3 plan; *tiles: how many of them the output is
+static int wgrad_class(int64_t M, int N, int K, int taps, long* tiles = nullptr) {
+    if (!(M > 0 && N > 0 && K > 0 && taps >= 1 && taps <= 64 && N % 4 == 0 && K % 4 == 0 && wgrad_use_x6(N, K))) return 0;
+    const WgradPlan p = plan_wgrad(M, N, K, taps, WG_H3);
+    if (tiles) *tiles = p.tiles;
+    if (p.tile == TILE_128) return 1;
+    if (p.tile == H3_TILE_256 && N % 256 == 0 && K % 256 == 0) return 2;
+    if (p.tile == TILE_128x96) return 3;            // 80 input channels: the decoder pre-net's first linear, the post-net's first convolution
+    if (p.tile == TILE_96x128) return 4;            // 80 output channels: the mel head, the post-net's last convolution
+    return 0;
+}
+
+// The workspace of a weight gradient in `nsplit` row splits, in floats: nsplit x taps partial products of N x K from 0 on, then
+// (from `colsum` on) nsplit rows of N column sums of dy -- the bias gradient's partial sums
+struct WgradLayout { size_t colsum; size_t floats; };
+static WgradLayout wgrad_layout(int nsplit, int N, int K, int taps) {
+    const size_t prod = (size_t)nsplit * taps * N * K;
+    return {prod, prod + (size_t)nsplit * N};
+}
+
+// One weight gradient dw[N][K] (x taps) (+)= dy[M][N]^T . x[M (row-shifted)][K] as its entry point states it
+struct WgradProblem {
+    const float *dy, *x; float* ws; size_t ws_bytes;
+    int64_t M; int N, K, taps;          // (a convolution entry gives B and T: M = B T, N = cout, K = cin)
+    int B, T, row_shift;                // utterances of T rows; a linear weight's x is read row_shift rows further inside them
+    const float *dy_amax, *x_amax;      // partial maxima of |dy| and |x| (fp16x3)
+    bool conv = false;                  // a same-padded convolution; else a linear weight
+    bool bias = false;                  // the column sums of dy are wanted
+};
+
+// the GemmArgs of a planned problem: C[N][K] (per tap) = dy^T[N][M] . xshift[M][K], partial products and column sums into pb.ws
+static GemmArgs wgrad_args(const WgradProblem& pb, WgradForm f, const WgradPlan& p) {
+    GemmArgs g = base_args();
+    g.A = pb.dy; g.B = pb.x; g.C = pb.ws; g.M = pb.N; g.N = pb.K; g.K = (int)pb.M;
+    g.lda = pb.N; g.ldb = pb.K; g.ldc = pb.K;
+    g.a_bytes = (uint32_t)((uint64_t)pb.M * pb.N * 4); g.b_bytes = (uint32_t)((uint64_t)pb.M * pb.K * 4);
+    // the shift of x's rows: a convolution's taps walk from -(taps - 1) / 2 on, one row per tap; a linear weight has the one shift
+    // its caller names, and utterances only then
+    g.T = (pb.conv || pb.row_shift != 0) ? pb.T : 0;
+    g.shift0 = pb.conv ? -((pb.taps - 1) / 2) : pb.row_shift; g.shift_step = pb.conv ? 1 : 0;
+    g.ztaps = pb.taps; g.kt_per_split = p.kt_per_split; g.c_zstride = (long)pb.N * pb.K;
+    g.colsum = pb.bias ? pb.ws + wgrad_layout(p.nsplit, pb.N, pb.K, pb.taps).colsum : nullptr;
+    if (f == WG_H3) {
+        g.a_amax = pb.dy_amax; g.a_amax_n = H3_AMAX_PARTIALS;
+        g.b_amax = pb.x_amax; g.b_amax_n = H3_AMAX_PARTIALS;
+    }
+    return g;
+}
+
+// the second stage: the partial products of pb.ws summed into dw, the column sums into dbias.  A linear weight's N rows may belong
+// to `nparts` destinations (equal row blocks; one pair of reductions per block), a convolution's are transposed to [co][ci][tap]
+static int wgrad_reduce(const WgradProblem& pb, const WgradPlan& p, const float* colsum, float* const* dw, float* const* dbias, int nparts,
+                        bool accumulate, hipStream_t stream, ttts_reduce_queue* queue) {
+    if (pb.conv) {
+        int rc = launch_conv_wgrad_reduce(pb.ws, dw[0], pb.N, pb.K, pb.taps, p.nsplit, accumulate, stream, queue);
+        if (rc == TTTS_OK && colsum) rc = launch_reduce_rows(colsum, pb.N, p.nsplit, pb.N, dbias[0], pb.N, nullptr, accumulate, stream, queue);
+        return rc;
+    }
+    const int Np = pb.N / nparts;
+    const long nk = (long)pb.N * pb.K, np = (long)Np * pb.K;
+    for (int i = 0; i < nparts; ++i) {
+        int rc = launch_reduce_rows_pair(pb.ws + (size_t)i * np, nk, p.nsplit, np, dw[i], colsum ? colsum + (size_t)i * Np : nullptr, pb.N, Np,
+                                         colsum ? dbias[i] : nullptr, accumulate, stream, queue);
+        if (rc) return rc;
+    }
+    return TTTS_OK;
+}
+
+#define ENTRY_REQUIRE(cond, fmt, ...) TTTS_REQUIRE(cond, "%s: " fmt, name, ##__VA_ARGS__)
+static int wgrad_check_operands(const char* name, const WgradProblem& pb) {
+    ENTRY_REQUIRE(aligned16(pb.dy) && aligned16(pb.x) && aligned16(pb.ws), "pointers must be 16-byte aligned");
+    ENTRY_REQUIRE((uint64_t)pb.M * pb.N * 4 < (1ull << 32) && (uint64_t)pb.M * pb.K * 4 < (1ull << 32), "operand larger than 4 GiB");
+    return TTTS_OK;
+}
+
+// A launch of its own: the three Linear entries, `parts` and the three convolution entries -- the form their name asks for (shapes the
+// split kernels do not take: the fp32-MFMA form, no maxima), then the second stage of one (dw, dbias), of a convolution, or per row block
+enum WgradStage2 { WG_PAIR, WG_CONV, WG_PARTS };
+static int wgrad_single(const char* name, WgradForm f, WgradStage2 stage, WgradProblem pb, float* const* dw, float* const* dbias,
+                        int nparts, int accumulate, ttts_reduce_queue* queue, void* stream) {
+    pb.conv = stage == WG_CONV;
+    ENTRY_REQUIRE(pb.dy && pb.x && pb.ws && dw && (stage == WG_PARTS || dw[0]), "null pointer");
+    ENTRY_REQUIRE(f != WG_H3 || (pb.dy_amax && pb.x_amax), "null pointer: dy_amax and x_amax (partial maxima of dy and x) are required");
+    if (pb.conv) {
+        ENTRY_REQUIRE(pb.B > 0 && pb.T > 0 && pb.K > 0 && pb.N > 0 && pb.taps > 0 && (pb.taps & 1), "bad dims B=%d T=%d cin=%d cout=%d taps=%d",
+                      pb.B, pb.T, pb.K, pb.N, pb.taps);
+        ENTRY_REQUIRE((long)pb.B * pb.T < (1L << 31), "B*T too large");
+        pb.M = (int64_t)pb.B * pb.T;
+    }
+    ENTRY_REQUIRE(pb.M > 0 && pb.N > 0 && pb.K > 0 && pb.M < (1LL << 31), "bad dims M=%lld N=%d K=%d", (long long)pb.M, pb.N, pb.K);
+    ENTRY_REQUIRE(pb.N % 4 == 0 && pb.K % 4 == 0, "%s=%d and %s=%d must be multiples of 4", pb.conv ? "cout" : "N", pb.N,
+                  pb.conv ? "cin" : "K", pb.K);
+    if (stage == WG_PARTS)
+        ENTRY_REQUIRE(nparts > 0 && nparts <= 64 && pb.N % nparts == 0 && (pb.N / nparts) % 4 == 0,
+                      "N=%d does not split in %d blocks of whole float4s", pb.N, nparts);
+    if (int rc = wgrad_check_operands(name, pb)) return rc;
+    ENTRY_REQUIRE(pb.ws_bytes >= ttts_wgrad_workspace_bytes(pb.M, pb.N, pb.K, pb.taps), "workspace too small");
+    ENTRY_REQUIRE(pb.conv || pb.row_shift == 0 || (pb.T > 0 && pb.M % pb.T == 0), "row_shift needs T>0 and M %% T == 0");
+    for (int i = 0; i < nparts; ++i) ENTRY_REQUIRE(dw[i] != nullptr, "null destination");
+    if (!wgrad_use_x6(pb.N, pb.K)) f = WG_F32;
+    pb.bias = dbias != nullptr && dbias[0] != nullptr;
+    const WgradPlan p = plan_wgrad(pb.M, pb.N, pb.K, pb.taps, f);
+    const GemmArgs g = wgrad_args(pb, f, p);
+    const int zdim = p.nsplit * pb.taps;
+    const int rc = f == WG_H3 ? dispatch_wgrad_h3(g, zdim, p.tile, (hipStream_t)stream)
+           : f == WG_X6 ? dispatch_wgrad_split(g, zdim, p.tile, (hipStream_t)stream)
+                        : dispatch_gemm<false, false>(g, zdim, p.tile, (hipStream_t)stream);
+    return rc ? rc : wgrad_reduce(pb, p, g.colsum, dw, dbias, nparts, accumulate != 0, (hipStream_t)stream, queue);
+}
+
 }  // namespace ttts
 
 using namespace ttts;
@@ -1023,208 +1154,113 @@ using namespace ttts;
 extern "C" {
 
 size_t ttts_wgrad_workspace_bytes(int64_t M, int N, int K, int taps) {
-    // covers both kernel forms (their row-split counts differ)
-    WgradPlan p = plan_wgrad(M, N, K, taps, false), q = plan_wgrad(M, N, K, taps, true), r = plan_wgrad(M, N, K, taps, true, HBK);
-    size_t ns = (size_t)(p.nsplit > q.nsplit ? p.nsplit : q.nsplit);
-    if ((size_t)r.nsplit > ns) ns = (size_t)r.nsplit;
-    return (ns * taps * N * K + ns * N) * sizeof(float);
-}
-
-static int wgrad_common(const float* dy, const float* x, float* ws, float* colsum_ws, int64_t M, int N, int K, int taps,
-                        int T, int shift0, int shift_step, WgradPlan* plan_out, bool x6, hipStream_t stream,
-                        const float* dy_amax = nullptr, const float* x_amax = nullptr) {
-    // dy_amax != NULL selects the fp16x3 kernel (32-row k-steps, dynamic pre-scales of dy and x); x6 must be true then
-    WgradPlan p = plan_wgrad(M, N, K, taps, x6, dy_amax ? HBK : BK);
-    GemmArgs g = base_args();
-    // C[N][K] (per tap) = dy^T[N][M] . xshift[M][K]
-    g.A = dy; g.B = x; g.C = ws; g.M = N; g.N = K; g.K = (int)M;
-    g.lda = N; g.ldb = K; g.ldc = K;
-    if (!((uint64_t)M * N * 4 < (1ull << 32) && (uint64_t)M * K * 4 < (1ull << 32))) {
-        set_error("weight gradient: operand larger than 4 GiB");
-        return TTTS_ERR_INVALID;
+    // The largest split count any launch can plan for this problem: the three forms of a launch of its own (their counts differ) and
+    // the grouped launches it may be a member of.  A member's count grows with the splits wanted per tile, target / tile total
+    // (plan_wgrad: fewer k-tiles per split, never fewer splits), and a group's tile total is at least the member's own: the worst
+    // group is the member ALONE -- or, for an output of fewer tiles than the 512-workgroup target asks for, the smallest group that
+    // reaches that target (wgrad_group_many tiles, a row range as long as another member may bring).  0 for a dimension that is none.
+    if (!(M > 0 && N > 0 && K > 0 && taps > 0)) return 0;
+    int ns = 0;
+    auto cover = [&](WgradForm f, const WgradGroup* grp) { const int n = plan_wgrad(M, N, K, taps, f, grp).nsplit; ns = n > ns ? n : ns; };
+    cover(WG_F32, nullptr); cover(WG_X6, nullptr); cover(WG_H3, nullptr);
+    long tiles = 0;
+    if (const int cls = wgrad_class(M, N, K, taps, &tiles)) {
+        const long many = wgrad_group_many(cls);
+        const WgradGroup alone = {cls, tiles, (long)((M + HBK - 1) / HBK)}, full = {cls, tiles < many ? many : tiles, WG_GROUP_NKT512};
+        cover(WG_H3, &alone); cover(WG_H3, &full);
     }
-    g.a_bytes = (uint32_t)((uint64_t)M * N * 4); g.b_bytes = (uint32_t)((uint64_t)M * K * 4);
-    g.T = T; g.shift0 = shift0; g.shift_step = shift_step; g.ztaps = taps;
-    g.kt_per_split = p.kt_per_split; g.c_zstride = (long)N * K;
-    g.colsum = colsum_ws;
-    *plan_out = p;
-    if (dy_amax) {
-        g.a_amax = dy_amax; g.a_amax_n = H3_AMAX_PARTIALS;
-        g.b_amax = x_amax; g.b_amax_n = H3_AMAX_PARTIALS;
-        return dispatch_wgrad_h3(g, p.nsplit * taps, p.tile, stream);
-    }
-    if (x6) return dispatch_wgrad_split(g, p.nsplit * taps, p.tile, stream);
-    return dispatch_gemm<false, false>(g, p.nsplit * taps, p.tile, stream);
+    return wgrad_layout(ns, N, K, taps).floats * sizeof(float);
 }
 
-static int linear_bwd_weight_impl(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes,
-                                  int64_t M, int N, int K, int row_shift, int T, int accumulate, bool x6,
-                                  ttts_reduce_queue* queue, void* stream_, const float* dy_amax = nullptr,
-                                  const float* x_amax = nullptr) {
-    // dw[N,K] (+)= dy[M,N]^T . x[M,K] ; dbias[N] (+)= column sums of dy
-    hipStream_t stream = (hipStream_t)stream_;
-    TTTS_REQUIRE(dy && x && dw && ws, "linear_bwd_weight: null pointer");
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear_bwd_weight: bad dims");
-    TTTS_REQUIRE(N % 4 == 0 && K % 4 == 0, "linear_bwd_weight: N=%d and K=%d must be multiples of 4", N, K);
-    TTTS_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(ws), "linear_bwd_weight: pointers must be 16-byte aligned");
-    TTTS_REQUIRE(ws_bytes >= ttts_wgrad_workspace_bytes(M, N, K, 1), "linear_bwd_weight: workspace too small");
-    TTTS_REQUIRE(row_shift == 0 || (T > 0 && M % T == 0), "linear_bwd_weight: row_shift needs T>0 and M %% T == 0");
-    WgradPlan p;
-    long n = (long)N * K;
-    x6 = x6 && wgrad_use_x6(N, K);
-    if (!x6) dy_amax = nullptr;
-    float* colsum_ws = dbias ? ws + (size_t)plan_wgrad(M, N, K, 1, x6, dy_amax ? HBK : BK).nsplit * n : nullptr;
-    int rc = wgrad_common(dy, x, ws, colsum_ws, M, N, K, 1, row_shift != 0 ? T : 0, row_shift, 0, &p, x6, stream, dy_amax, x_amax);
-    if (rc) return rc;
-    return launch_reduce_rows_pair(ws, n, p.nsplit, n, dw, colsum_ws, N, N, dbias, accumulate != 0, stream, queue);
-}
-
+// dw[N,K] (+)= dy[M,N]^T . x[M,K] ; dbias[N] (+)= column sums of dy     ({...}: a WgradProblem up to its maxima)
 int ttts_linear_bwd_weight(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes,
                            int64_t M, int N, int K, int row_shift, int T, int accumulate, ttts_reduce_queue* queue, void* stream) {
-    return linear_bwd_weight_impl(dy, x, dw, dbias, ws, ws_bytes, M, N, K, row_shift, T, accumulate, false, queue, stream);
+    return wgrad_single("linear_bwd_weight", WG_F32, WG_PAIR, {dy, x, ws, ws_bytes, M, N, K, 1, 0, T, row_shift, nullptr, nullptr}, &dw, &dbias, 1,
+                        accumulate, queue, stream);
 }
 int ttts_linear_bwd_weight_x6(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes,
                               int64_t M, int N, int K, int row_shift, int T, int accumulate, ttts_reduce_queue* queue, void* stream) {
-    return linear_bwd_weight_impl(dy, x, dw, dbias, ws, ws_bytes, M, N, K, row_shift, T, accumulate, true, queue, stream);
+    return wgrad_single("linear_bwd_weight_x6", WG_X6, WG_PAIR, {dy, x, ws, ws_bytes, M, N, K, 1, 0, T, row_shift, nullptr, nullptr}, &dw, &dbias, 1,
+                        accumulate, queue, stream);
 }
 int ttts_linear_bwd_weight_h3(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes,
                               int64_t M, int N, int K, int row_shift, int T, int accumulate, const float* dy_amax,
                               const float* x_amax, ttts_reduce_queue* queue, void* stream) {
-    TTTS_REQUIRE(dy_amax && x_amax, "linear_bwd_weight_h3: dy_amax and x_amax (partial maxima of dy and x) are required");
-    return linear_bwd_weight_impl(dy, x, dw, dbias, ws, ws_bytes, M, N, K, row_shift, T, accumulate, true, queue, stream, dy_amax,
-                                  x_amax);
+    return wgrad_single("linear_bwd_weight_h3", WG_H3, WG_PAIR, {dy, x, ws, ws_bytes, M, N, K, 1, 0, T, row_shift, dy_amax, x_amax}, &dw, &dbias, 1,
+                        accumulate, queue, stream);
 }
 
+// ONE weight-gradient GEMM dy^T x (N x K) whose N rows belong to `nparts` different weights (equal row blocks): block i is reduced into
+// dw_parts[i] ((N / nparts) x K, contiguous), its column sums into dbias_parts[i] -- the fused K/V projection of all decoder layers'
+// cross-attention (model/layers.py:54-74 runs it once per layer on the same memory)
 int ttts_linear_bwd_weight_h3_parts(const float* dy, const float* x, float* const* dw_parts, float* const* dbias_parts, int nparts,
                                     float* ws, size_t ws_bytes, int64_t M, int N, int K, int accumulate, const float* dy_amax,
-                                    const float* x_amax, ttts_reduce_queue* queue, void* stream_) {
-    // ONE weight-gradient GEMM dy^T x (N x K) whose N rows belong to `nparts` different weights (equal row blocks): block i is
-    // reduced into dw_parts[i] ((N / nparts) x K, contiguous) and its column sums into dbias_parts[i] -- the fused K/V
-    // projection of all decoder layers' cross-attention (model/layers.py:54-74 runs it once per layer on the same memory)
-    hipStream_t stream = (hipStream_t)stream_;
-    TTTS_REQUIRE(dy && x && dw_parts && ws && dy_amax && x_amax, "linear_bwd_weight_h3_parts: null pointer");
-    TTTS_REQUIRE(nparts > 0 && nparts <= 64 && N % nparts == 0 && (N / nparts) % 4 == 0, "linear_bwd_weight_h3_parts: N=%d does not split in %d blocks of whole float4s", N, nparts);
-    TTTS_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1LL << 31) && K % 4 == 0, "linear_bwd_weight_h3_parts: bad dims");
-    TTTS_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(ws), "linear_bwd_weight_h3_parts: pointers must be 16-byte aligned");
-    TTTS_REQUIRE(ws_bytes >= ttts_wgrad_workspace_bytes(M, N, K, 1), "linear_bwd_weight_h3_parts: workspace too small");
-    for (int i = 0; i < nparts; ++i) TTTS_REQUIRE(dw_parts[i] != nullptr, "linear_bwd_weight_h3_parts: null destination");
-    WgradPlan p;
-    const long n = (long)N * K;
-    const bool x6 = wgrad_use_x6(N, K);
-    const bool want_b = dbias_parts != nullptr && dbias_parts[0] != nullptr;
-    float* colsum_ws = want_b ? ws + (size_t)plan_wgrad(M, N, K, 1, x6, x6 ? HBK : BK).nsplit * n : nullptr;
-    int rc = wgrad_common(dy, x, ws, colsum_ws, M, N, K, 1, 0, 0, 0, &p, x6, stream, x6 ? dy_amax : nullptr, x_amax);
-    if (rc) return rc;
-    const int Np = N / nparts;
-    const long np = (long)Np * K;
-    for (int i = 0; i < nparts; ++i) {
-        rc = launch_reduce_rows_pair(ws + (size_t)i * np, n, p.nsplit, np, dw_parts[i], want_b ? colsum_ws + (size_t)i * Np : nullptr, N, Np,
-                                     want_b ? dbias_parts[i] : nullptr, accumulate != 0, stream, queue);
-        if (rc) return rc;
-    }
-    return TTTS_OK;
+                                    const float* x_amax, ttts_reduce_queue* queue, void* stream) {
+    return wgrad_single("linear_bwd_weight_h3_parts", WG_H3, WG_PARTS, {dy, x, ws, ws_bytes, M, N, K, 1, 0, 0, 0, dy_amax, x_amax}, dw_parts,
+                        dbias_parts, nparts, accumulate, queue, stream);
 }
 
-int ttts_wgrad_group_ok(int64_t M, int N, int K, int taps) {
-    // can dw[N,K(,tap)] = dy[M,N]^T x[M(+tap shift),K] be a member of a grouped launch, and of which CLASS (members of one launch
-    // share it)?  1: the fp16x3 form on the 4-wave 128 x 128 tile (small outputs); 2: whole 256 x 256 tiles on the 8-wave LDS-DMA
-    // kernel (long row ranges); 3 / 4: the 96-wide tiles of the 80-channel mel side; 0: none (the fp32-MFMA shapes, ragged
-    // 256-tiles keep launches of their own).  taps = 1: a linear weight; taps > 1: a convolution's (cout = N, cin = K).
-    if (!(M > 0 && N > 0 && K > 0 && taps >= 1 && taps <= 64 && N % 4 == 0 && K % 4 == 0 && wgrad_use_x6(N, K))) return 0;
-    const int tile = plan_wgrad(M, N, K, taps, true, HBK).tile;
-    if (tile == TILE_128) return 1;
-    if (tile == H3_TILE_256 && N % 256 == 0 && K % 256 == 0) return 2;
-    if (tile == TILE_128x96) return 3;            // 80 input channels: the decoder pre-net's first linear, the post-net's first convolution
-    if (tile == TILE_96x128) return 4;            // 80 output channels: the mel head, the post-net's last convolution
-    return 0;
+// dw[co,ci,tap] (+)= sum_{b,t} dy[b,t,co] * x[b,t+tap-pad,ci] ; dbias[co] (+)= sum dy
+int ttts_conv1d_bwd_weight(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
+                           int T, int cin, int cout, int taps, int accumulate, ttts_reduce_queue* queue, void* stream) {
+    return wgrad_single("conv1d_bwd_weight", WG_F32, WG_CONV, {dy, x, ws, ws_bytes, 0, cout, cin, taps, B, T, 0, nullptr, nullptr}, &dw, &dbias, 1,
+                        accumulate, queue, stream);
+}
+int ttts_conv1d_bwd_weight_x6(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
+                              int T, int cin, int cout, int taps, int accumulate, ttts_reduce_queue* queue, void* stream) {
+    return wgrad_single("conv1d_bwd_weight_x6", WG_X6, WG_CONV, {dy, x, ws, ws_bytes, 0, cout, cin, taps, B, T, 0, nullptr, nullptr}, &dw, &dbias, 1,
+                        accumulate, queue, stream);
+}
+int ttts_conv1d_bwd_weight_h3(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
+                              int T, int cin, int cout, int taps, int accumulate, const float* dy_amax, const float* x_amax,
+                              ttts_reduce_queue* queue, void* stream) {
+    return wgrad_single("conv1d_bwd_weight_h3", WG_H3, WG_CONV, {dy, x, ws, ws_bytes, 0, cout, cin, taps, B, T, 0, dy_amax, x_amax}, &dw, &dbias, 1,
+                        accumulate, queue, stream);
 }
 
+int ttts_wgrad_group_ok(int64_t M, int N, int K, int taps) { return wgrad_class(M, N, K, taps); }
+
+// n <= 4 independent weight gradients as ONE grid (all members of one class, ttts_wgrad_group_ok).  Member i is the problem of
+// ttts_linear_bwd_weight_h3 (taps_i = 1; row_shift_i / T_i as its row_shift / T -- the decoder pre-net's go-frame shift) or of
+// ttts_conv1d_bwd_weight_h3 (taps_i > 1, M_i = B T_i).  The row splits are planned for the group (same chip-filling target as a
+// single launch, shared by the members), so every member writes 1/n of the partial sums a launch of its own would and its
+// workgroups walk n times the rows.  Each member's partial sums go to its own workspace and are reduced (queued) as a single one's.
 int ttts_wgrad_group(int n, const float* const* dy, const float* const* x, float* const* dw, float* const* dbias,
                      float* const* ws, const size_t* ws_bytes, const int64_t* M, const int* N, const int* K, const int* taps,
                      const int* T, const int* row_shift, int accumulate, const float* const* dy_amax, const float* const* x_amax,
                      ttts_reduce_queue* queue, void* stream_) {
-    // n <= 4 independent weight gradients as ONE grid (all members of one class, ttts_wgrad_group_ok).  Member i with taps_i = 1:
-    // dw_i[N_i,K_i] (+)= dy_i^T x_i (a linear weight; row_shift_i != 0: x_i read row_shift_i rows further inside utterances of T_i
-    // rows, as ttts_linear_bwd_weight's row_shift -- the decoder pre-net's go-frame shift); taps_i > 1: dw_i[N_i,K_i,tap] (+)= sum over (b, t) of dy_i[b,t,:] x_i[b,
-    // t + tap - (taps-1)/2, :] with utterances of T_i rows (a same-padded convolution; M_i = B T_i).  dbias_i (+)= column sums of
-    // dy_i.  The row splits are planned for the group (same chip-filling target as a single launch, shared by the members), so
-    // every member writes 1/n of the partial sums a launch of its own would and its workgroups walk n times the rows.  Each
-    // member's partial sums go to its own workspace and are reduced (queued) as usual.
+    const char* name = "wgrad_group";
     hipStream_t stream = (hipStream_t)stream_;
-    TTTS_REQUIRE(n >= 1 && n <= 4 && dy && x && dw && ws && ws_bytes && M && N && K && taps && T && row_shift && dy_amax && x_amax, "wgrad_group: bad arguments");
-    GemmArgs gs[4];
-    int zd[4], ns[4];
-    float* colsum[4];
-    long tiles_total = 0, nkt_max = 0;
-    const int cls = ttts_wgrad_group_ok(M[0], N[0], K[0], taps[0]);
-    const int edge_n = cls == 2 ? 256 : cls == 4 ? 96 : 128, edge_k = cls == 2 ? 256 : cls == 3 ? 96 : 128;      // tile: output rows x columns
-    const int tile = cls == 3 ? TILE_128x96 : cls == 4 ? TILE_96x128 : TILE_128;
+    ENTRY_REQUIRE(n >= 1 && n <= WG_GROUP_MAX && dy && x && dw && ws && ws_bytes && M && N && K && taps && T && row_shift && dy_amax && x_amax,
+                  "bad arguments");
+    WgradProblem pb[WG_GROUP_MAX]; WgradPlan plan[WG_GROUP_MAX]; GemmArgs gs[WG_GROUP_MAX]; int zd[WG_GROUP_MAX];      // (zd: row splits x taps)
+    WgradGroup grp = {wgrad_class(M[0], N[0], K[0], taps[0]), 0, 0};
     for (int i = 0; i < n; ++i) {
-        TTTS_REQUIRE(dy[i] && x[i] && dw[i] && ws[i] && dy_amax[i] && x_amax[i], "wgrad_group: null pointer (member %d)", i);
-        TTTS_REQUIRE(cls != 0 && ttts_wgrad_group_ok(M[i], N[i], K[i], taps[i]) == cls && M[i] < (1LL << 31),
-                     "wgrad_group: member %d (M=%lld N=%d K=%d taps=%d) is not of the group's class %d", i, (long long)M[i], N[i], K[i], taps[i], cls);
-        TTTS_REQUIRE((taps[i] == 1 && row_shift[i] == 0) || (T[i] > 0 && M[i] % T[i] == 0 && (cls != 2 || T[i] >= 16)),
-                     "wgrad_group: member %d: a convolution / a shifted linear needs its utterance length", i);
-        TTTS_REQUIRE(taps[i] == 1 || row_shift[i] == 0, "wgrad_group: member %d: a convolution takes no row shift of its own", i);
-        TTTS_REQUIRE(aligned16(dy[i]) && aligned16(x[i]) && aligned16(ws[i]), "wgrad_group: pointers must be 16-byte aligned");
-        TTTS_REQUIRE((uint64_t)M[i] * N[i] * 4 < (1ull << 32) && (uint64_t)M[i] * K[i] * 4 < (1ull << 32), "wgrad_group: operand larger than 4 GiB");
-        tiles_total += (long)cdiv(N[i], edge_n) * cdiv(K[i], edge_k) * taps[i];
-        const long nkt = (M[i] + HBK - 1) / HBK;
-        nkt_max = nkt > nkt_max ? nkt : nkt_max;
+        pb[i] = {dy[i], x[i], ws[i], ws_bytes[i], M[i], N[i], K[i], taps[i], 0, T[i], row_shift[i], dy_amax[i], x_amax[i], taps[i] > 1,
+                 dbias != nullptr && dbias[i] != nullptr};
+        ENTRY_REQUIRE(dy[i] && x[i] && dw[i] && ws[i] && dy_amax[i] && x_amax[i], "null pointer (member %d)", i);
+        long tiles = 0;
+        ENTRY_REQUIRE(grp.cls != 0 && wgrad_class(M[i], N[i], K[i], taps[i], &tiles) == grp.cls && M[i] < (1LL << 31),
+                      "member %d (M=%lld N=%d K=%d taps=%d) is not of the group's class %d", i, (long long)M[i], N[i], K[i], taps[i], grp.cls);
+        if (int rc = wgrad_check_operands(name, pb[i])) return rc;
+        grp.tiles_total += tiles;
+        if ((M[i] + HBK - 1) / HBK > grp.nkt_max) grp.nkt_max = (M[i] + HBK - 1) / HBK;
     }
-    // plan_wgrad's rule for the class, applied to the group as a whole: the 8-wave tile holds one workgroup per CU, the 4-wave
-    // tile two (a second round only for many tiles over long row ranges)
-    // (the 96-wide tiles' workgroups are long -- 10 + 2 tiles of the mel side over 55 680 rows were 140 us on 252 workgroups -- and
-    // their partial tiles small: both workgroup slots of every CU from 8 tiles on)
-    const long many = (cls == 3 || cls == 4) ? 8 : 13;
-    // (row ranges from 200 k-tiles on -- 6 400 rows: at 13 920 rows a group on ONE workgroup slot per CU ran its 109 k-tiles per
-    // workgroup at a fifth of the MFMA rate, nothing covering its operand latencies: batch 16 -0.08 ms, `profiles/r06_ab_wgrad_target.txt`)
-#ifndef TTTS_WG_NKT512
-#define TTTS_WG_NKT512 200
-#endif
-    const long target = cls == 2 ? 256 : ((tiles_total >= many && nkt_max >= TTTS_WG_NKT512) ? 512 : 256);
-    long want = target / tiles_total;
-    if (want < 1) want = 1;
     for (int i = 0; i < n; ++i) {
-        const long nkt = (M[i] + HBK - 1) / HBK;
-        long w = want > nkt ? nkt : want;
-        long per = (nkt + w - 1) / w;
-        if (per < 8 && nkt >= 8) per = 8;
-        const int nsplit = (int)((nkt + per - 1) / per);
-        const long nk = (long)N[i] * K[i];
-        TTTS_REQUIRE(ws_bytes[i] >= ((size_t)nsplit * taps[i] * nk + (size_t)nsplit * N[i]) * sizeof(float), "wgrad_group: workspace %d too small", i);
-        GemmArgs g = base_args();
-        g.A = dy[i]; g.B = x[i]; g.C = ws[i]; g.M = N[i]; g.N = K[i]; g.K = (int)M[i];
-        g.lda = N[i]; g.ldb = K[i]; g.ldc = K[i];
-        g.a_bytes = (uint32_t)((uint64_t)M[i] * N[i] * 4); g.b_bytes = (uint32_t)((uint64_t)M[i] * K[i] * 4);
-        const bool conv = taps[i] > 1;
-        g.T = (conv || row_shift[i] != 0) ? T[i] : 0; g.shift0 = conv ? -((taps[i] - 1) / 2) : row_shift[i]; g.shift_step = conv ? 1 : 0;
-        g.ztaps = taps[i];
-        g.kt_per_split = (int)per; g.c_zstride = nk;
-        colsum[i] = (dbias != nullptr && dbias[i] != nullptr) ? ws[i] + (size_t)nsplit * taps[i] * nk : nullptr;
-        g.colsum = colsum[i];
-        g.a_amax = dy_amax[i]; g.a_amax_n = H3_AMAX_PARTIALS;
-        g.b_amax = x_amax[i]; g.b_amax_n = H3_AMAX_PARTIALS;
-        gs[i] = g;
-        ns[i] = nsplit;
-        zd[i] = nsplit * taps[i];
+        plan[i] = plan_wgrad(M[i], N[i], K[i], taps[i], WG_H3, &grp);
+        ENTRY_REQUIRE(ws_bytes[i] >= wgrad_layout(plan[i].nsplit, N[i], K[i], taps[i]).floats * sizeof(float), "workspace %d too small", i);
+        ENTRY_REQUIRE((taps[i] == 1 && row_shift[i] == 0) || (T[i] > 0 && M[i] % T[i] == 0 && (grp.cls != 2 || T[i] >= 16)),
+                      "member %d: a convolution / a shifted linear needs its utterance length", i);
+        ENTRY_REQUIRE(taps[i] == 1 || row_shift[i] == 0, "member %d: a convolution takes no row shift of its own", i);
+        gs[i] = wgrad_args(pb[i], WG_H3, plan[i]);
+        zd[i] = plan[i].nsplit * taps[i];
     }
-    int rc = cls == 2 ? launch_wgrad_dma_group(gs, zd, n, stream) : launch_wgrad_h3_group(gs, zd, n, tile, stream);
-    if (rc) return rc;
-    for (int i = 0; i < n; ++i) {
-        const long nk = (long)N[i] * K[i];
-        if (taps[i] == 1) {
-            rc = launch_reduce_rows_pair(ws[i], nk, ns[i], nk, dw[i], colsum[i], N[i], N[i], colsum[i] ? dbias[i] : nullptr, accumulate != 0,
-                                         stream, queue);
-        } else {
-            rc = launch_conv_wgrad_reduce(ws[i], dw[i], N[i], K[i], taps[i], ns[i], accumulate != 0, stream, queue);
-            if (rc == TTTS_OK && colsum[i])
-                rc = launch_reduce_rows(colsum[i], N[i], ns[i], N[i], dbias[i], N[i], nullptr, accumulate != 0, stream, queue);
-        }
-        if (rc) return rc;
-    }
-    return TTTS_OK;
+    int rc = grp.cls == 2 ? launch_wgrad_dma_group(gs, zd, n, stream) : launch_wgrad_h3_group(gs, zd, n, plan[0].tile, stream);
+    for (int i = 0; i < n && rc == TTTS_OK; ++i)
+        rc = wgrad_reduce(pb[i], plan[i], gs[i].colsum, dw + i, dbias ? dbias + i : nullptr, 1, accumulate != 0, stream, queue);
+    return rc;
 }
+#undef ENTRY_REQUIRE
 
 size_t ttts_conv1d_pack_bytes(int cout, int cin, int taps) { return (size_t)cout * cin * taps * sizeof(float); }
 
@@ -1235,46 +1271,6 @@ int ttts_conv1d_pack_weight(const float* w, float* w_fwd, float* w_bwd, int cout
                        cout, cin, taps);
     TTTS_LAUNCH_CHECK("conv_pack_weight_kernel");
     return TTTS_OK;
-}
-
-static int conv1d_bwd_weight_impl(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
-                                  int T, int cin, int cout, int taps, int accumulate, bool x6, ttts_reduce_queue* queue,
-                                  void* stream_, const float* dy_amax = nullptr, const float* x_amax = nullptr) {
-    // dw[co,ci,tap] (+)= sum_{b,t} dy[b,t,co] * x[b,t+tap-pad,ci] ; dbias[co] (+)= sum dy
-    hipStream_t stream = (hipStream_t)stream_;
-    TTTS_REQUIRE(dy && x && dw && ws, "conv1d_bwd_weight: null pointer");
-    TTTS_REQUIRE(cin % 4 == 0 && cout % 4 == 0, "conv1d_bwd_weight: channel counts must be multiples of 4");
-    TTTS_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(ws), "conv1d_bwd_weight: pointers must be 16-byte aligned");
-    int64_t M = (int64_t)B * T;
-    TTTS_REQUIRE(ws_bytes >= ttts_wgrad_workspace_bytes(M, cout, cin, taps), "conv1d_bwd_weight: workspace too small");
-    WgradPlan p;
-    long n = (long)cout * cin * taps;
-    x6 = x6 && wgrad_use_x6(cout, cin);
-    if (!x6) dy_amax = nullptr;
-    float* colsum_ws = dbias ? ws + (size_t)plan_wgrad(M, cout, cin, taps, x6, dy_amax ? HBK : BK).nsplit * n : nullptr;
-    int rc = wgrad_common(dy, x, ws, colsum_ws, M, cout, cin, taps, T, -((taps - 1) / 2), 1, &p, x6, stream, dy_amax, x_amax);
-    if (rc) return rc;
-    rc = launch_conv_wgrad_reduce(ws, dw, cout, cin, taps, p.nsplit, accumulate != 0, stream, queue);
-    if (rc == TTTS_OK && dbias)
-        rc = launch_reduce_rows(colsum_ws, cout, p.nsplit, cout, dbias, cout, nullptr, accumulate != 0, stream, queue);
-    return rc;
-}
-
-int ttts_conv1d_bwd_weight(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
-                           int T, int cin, int cout, int taps, int accumulate, ttts_reduce_queue* queue, void* stream) {
-    return conv1d_bwd_weight_impl(dy, x, dw, dbias, ws, ws_bytes, B, T, cin, cout, taps, accumulate, false, queue, stream);
-}
-int ttts_conv1d_bwd_weight_x6(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
-                              int T, int cin, int cout, int taps, int accumulate, ttts_reduce_queue* queue, void* stream) {
-    return conv1d_bwd_weight_impl(dy, x, dw, dbias, ws, ws_bytes, B, T, cin, cout, taps, accumulate, true, queue, stream);
-}
-
-int ttts_conv1d_bwd_weight_h3(const float* dy, const float* x, float* dw, float* dbias, float* ws, size_t ws_bytes, int B,
-                              int T, int cin, int cout, int taps, int accumulate, const float* dy_amax, const float* x_amax,
-                              ttts_reduce_queue* queue, void* stream) {
-    TTTS_REQUIRE(dy_amax && x_amax, "conv1d_bwd_weight_h3: dy_amax and x_amax (partial maxima of dy and x) are required");
-    return conv1d_bwd_weight_impl(dy, x, dw, dbias, ws, ws_bytes, B, T, cin, cout, taps, accumulate, true, queue, stream, dy_amax,
-                                  x_amax);
 }
 
 int ttts_gemm_tile_choice(int64_t M, int N, int K, int x6) {

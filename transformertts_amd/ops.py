@@ -10,7 +10,7 @@ from __future__ import annotations
 import os
 import weakref
 from ctypes import c_void_p
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -395,12 +395,30 @@ WGRAD_SIDE_STREAM = False
 WGRAD_SIDE_MAX_ROWS = 0      # > 0: only groups over at most this many rows take the side stream (the small-batch / encoder groups)
 
 
+class WgradMember(NamedTuple):
+    """one weight gradient that waits for its grouped launch: dw (+)= dy^T x, db (+)= column sums of dy -- the fields are the
+    per-member arguments of ttts_wgrad_group (`ws`: its partial sums, ttts_wgrad_workspace_bytes; `db` may be None)"""
+    dy: torch.Tensor
+    dy_amax: torch.Tensor
+    x: torch.Tensor
+    x_amax: torch.Tensor
+    dw: torch.Tensor
+    db: Optional[torch.Tensor]
+    M: int
+    N: int
+    K: int
+    ws: torch.Tensor
+    taps: int
+    T: int
+    row_shift: int
+
+
 class ReduceQueue:
     """Host-side queue of deferred second-stage reductions (include/ttts_hip.h, ttts_reduce_queue) plus the workspaces
     the queued reductions still read -- and, in front of it, the small weight gradients that wait to be launched as a GROUP
     (`defer_wgrad`): a parameter gradient has no reader before the optimizer, so the 256 x 256-class outputs of a layer
     (out-projections, the cross-attention query projection, the encoder's linears) are collected as backward produces their
-    operands and run as ONE grid of up to WGRAD_GROUP_MAX problems (ttts_linear_bwd_weight_h3_group): 1/n of the partial sums,
+    operands and run as ONE grid of up to WGRAD_GROUP_MAX problems (ttts_wgrad_group): 1/n of the partial sums,
     n times the rows per workgroup, 1/n of the launches."""
 
     def __init__(self):
@@ -433,11 +451,11 @@ class ReduceQueue:
         workgroups then walk equally long row ranges."""
         self._arm()
         pend = self.wg[cls]
-        if pend and (pend[0][6] != M or pend[0][0].device != dy.device):
+        if pend and (pend[0].M != M or pend[0].dy.device != dy.device):
             self.launch_wgrads(cls)
             pend = self.wg[cls]
         ws = _ws(self._lib.ttts_wgrad_workspace_bytes(M, N, K, taps), x.device)
-        pend.append((dy, dy_am, x, x_am, dw, db, M, N, K, ws, taps, T, row_shift))
+        pend.append(WgradMember(dy, dy_am, x, x_am, dw, db, M, N, K, ws, taps, T, row_shift))
         if len(pend) >= WGRAD_GROUP_SIZE[cls]:
             self.launch_wgrads(cls)
 
@@ -453,15 +471,15 @@ class ReduceQueue:
         wg, self.wg[cls] = self.wg[cls], []
         n = len(wg)
         PA, ZA, LA, IA = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n, ctypes.c_int * n
-        col = lambda i: [m[i] for m in wg]      # noqa: E731
         ptr = lambda ts: PA(*[(t.data_ptr() if t is not None else None) for t in ts])      # noqa: E731
+        dy, dy_amax, x, x_amax, dw, db, M, N, K, ws, taps, T, row_shift = zip(*wg)
+
         def go(stream):
             _lib.check(self._lib.ttts_wgrad_group(
-                n, ptr(col(0)), ptr(col(2)), ptr(col(4)), ptr(col(5)), ptr(col(9)), ZA(*[m[9].numel() * 4 for m in wg]), LA(*col(6)),
-                IA(*col(7)), IA(*col(8)), IA(*col(10)), IA(*col(11)), IA(*col(12)), 1, ptr(col(1)), ptr(col(3)),
-                self.handle if DEFER_REDUCE else None, stream), "ttts_wgrad_group")
-        if WGRAD_SIDE_STREAM and DEFER_REDUCE and (WGRAD_SIDE_MAX_ROWS <= 0 or wg[0][6] <= WGRAD_SIDE_MAX_ROWS):
-            dev = wg[0][0].device
+                n, ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), ZA(*[w.numel() * 4 for w in ws]), LA(*M), IA(*N), IA(*K), IA(*taps),
+                IA(*T), IA(*row_shift), 1, ptr(dy_amax), ptr(x_amax), self.handle if DEFER_REDUCE else None, stream), "ttts_wgrad_group")
+        if WGRAD_SIDE_STREAM and DEFER_REDUCE and (WGRAD_SIDE_MAX_ROWS <= 0 or M[0] <= WGRAD_SIDE_MAX_ROWS):
+            dev = dy[0].device
             if self._side is None or self._side.device != dev:
                 self._side = torch.cuda.Stream(device=dev)
             cur = torch.cuda.current_stream(dev)
@@ -470,10 +488,10 @@ class ReduceQueue:
                 go(c_void_p(self._side.cuda_stream))
             self._side_busy = True
             # the operands were allocated on the main stream: they must outlive the side stream's reads -- kept until the join
-            self.keep.extend(t for m in wg for t in (m[0], m[1], m[2], m[3]))
+            self.keep.extend(t for m in wg for t in (m.dy, m.dy_amax, m.x, m.x_amax))
         else:
             go(_stream())
-        self.keep.extend(m[9] for m in wg)
+        self.keep.extend(ws)
 
     def join_side(self) -> None:
         if self._side_busy:
