@@ -677,6 +677,31 @@ int ttts_istft(const float* spec, const int64_t* frames, int B, int Tmax, int n_
 int ttts_stft_project(const float* wave, int64_t ld_batch, const int64_t* wave_lens, const int64_t* frames, int B, int Nmax, int n_fft,
                       int hop, const void* tables, const float* mag, float* prev, float momentum, float* spec, int64_t* frames_out,
                       void* stream);
+/* ---- Band-limited resampler: a ragged batch of waveforms from one rate to another (resample.hip; additive, the ABI version
+ * stays 24): windowed-sinc (Kaiser) interpolation in polyphase form, the family of resampy's kaiser_best and torchaudio's
+ * sinc_interp_kaiser, restated from the definition.
+ *   rates       g = gcd(orig, new), L = new / g, M = orig / g, L != M; cutoff s = rolloff * min(1, L / M)
+ *   kernel      k(u) = sinc(u) * w(u / zeros), sinc(u) = sin(pi u) / (pi u), w(v) = I0(beta sqrt(1 - v^2)) / I0(beta) for |v| < 1,
+ *               else 0; W = ceil(zeros / s), K = 2 W + 2 taps
+ *   table       h[r][k] = s * k(s * ((W - k) + p_r / L)), p_r = (r M) mod L, built by the caller in fp64 and rounded to fp32 once,
+ *               tap-major: table[k * L + r], L * K floats.  ttts_resample_table_check reads a HOST copy: the size, finite values,
+ *               K even and at least 4, gcd(L, M) == 1.
+ *   sum         output j of utterance b sits at input time j M / L: q = floor(j M / L) (formed in 64 bits), r = j mod L,
+ *               y[b, j] = sum_{k = 0 .. K-1} table[k * L + r] * x[b, q - W + k], ascending k, fp32 fused multiply-adds from 0;
+ *               x[b, i] counts as 0 for i < 0 or i >= len_b and such a sample is never loaded
+ *   lengths     len_b = wave_lens[b] clamped to [0, Nmax]; out_lens[b] = ceil(len_b L / M) (int64, written); out is (B, Nout) at
+ *               stride ld_out with Nout = ceil(Nmax L / M); samples from out_lens[b] to Nout are zeros
+ * One launch, grid (ceil(Nout / tile), B) with tile = ttts_resample_tile outputs per workgroup; a workgroup wholly behind
+ * out_lens[b] only writes its zeros.  No host read, no allocation, no atomics, the same bits whatever the grid, the batch or the
+ * call, capturable into a HIP graph.  Refused before any launch, with a message that names the value: null pointers, B < 1 or
+ * B > 65535 (the grid), Nmax < 1 or Nmax > 2^30, L < 1 or M < 1, L == M, L > 1024 (the table), max(L / M, M / L) > 8 and K > 1280
+ * (the input span a workgroup stages: at most 1023 * 8 + 2 + 1280 floats of LDS), K odd or K < 4, strides that do not cover a
+ * row, misaligned pointers (4 bytes; 8 for the int64 arrays). */
+size_t ttts_resample_table_bytes(int L, int K);
+int ttts_resample_table_check(const void* host_table, size_t bytes, int L, int M, int K);
+int ttts_resample_tile(void);
+int ttts_resample(const float* wave, int64_t ld_batch, const int64_t* wave_lens, int B, int Nmax, int L, int M, int K,
+                  const float* table, float* out, int64_t ld_out, int64_t* out_lens, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -2,10 +2,12 @@
 """A directory of recordings -> the `.npz` files `TransformerTTSDataset` trains from (the mel half of the reference's
 `preprocess.py:28-72`), through `MelFrontEnd` (csrc/audio.hip).
 
-    python tools/preprocess_mel.py --config config.yaml [--batch 64] [--sequences DIR] [--stats stats.json]
+    python tools/preprocess_mel.py --config config.yaml [--batch 64] [--sequences DIR] [--stats stats.json] [--resample]
 
-Reads `config['path']['data']/wavs/*.wav` (mono, at `config['audio']['sample_rate']`: there is no resampler) and writes one
-`<id>.npz` per recording into `config['path']['preprocessed']`.  With `config['audio']['normalize_mel']` a first pass over the
+Reads `config['path']['data']/wavs/*.wav` (mono; at `config['audio']['sample_rate']`, or with `--resample` at any rate: the
+recordings of a batch that are at another rate are grouped by their rate and brought to the config's on the device by
+`audio.Resampler`, csrc/resample.hip, one resampler per distinct rate, before the front end; without the flag such a file is
+refused as before) and writes one `<id>.npz` per recording into `config['path']['preprocessed']`.  With `config['audio']['normalize_mel']` a first pass over the
 batches adds sum, sum of squares and count of the unnormalised log-mels, mean = S / n, std = sqrt(Q / n - mean^2 + 1e-8), written
 to the `--stats` file with the keys `mean` and `std`; the second pass writes `melspec (n_mels, T)` fp32, normalised with them.
 Phonemisation is not done here (it needs `g2p_en`): `--sequences DIR` copies `transcript`, `phoneme` and `sequence` from the
@@ -30,12 +32,48 @@ def make_front_end(audio_config):
     return audio.MelFrontEnd(audio_config)
 
 
-def batches(paths, batch, sample_rate, min_len, log):
+def make_resampler(orig_rate, new_rate):
+    return audio.Resampler(orig_rate, new_rate)
+
+
+def _pad(sigs):
+    wave = np.zeros((len(sigs), max(s.size for s in sigs)), dtype=np.float32)
+    for b, s in enumerate(sigs):
+        wave[b, :s.size] = s
+    return wave
+
+
+def read_resampled(paths, sample_rate, resamplers):
+    """the recordings at `sample_rate`: those at another rate go, one padded batch per native rate, through that rate's
+    resampler (made on first use and kept in `resamplers`)"""
+    sigs, by_rate = [None] * len(paths), {}
+    for i, p in enumerate(paths):
+        x, rate = audio.read_wav_native(p)
+        if rate == int(sample_rate) or x.size == 0:
+            sigs[i] = x
+        else:
+            by_rate.setdefault(rate, []).append((i, x))
+    for rate, group in sorted(by_rate.items()):
+        if rate not in resamplers:
+            resamplers[rate] = make_resampler(rate, int(sample_rate))
+        rs = resamplers[rate]
+        wave = torch.from_numpy(_pad([x for _, x in group]))
+        out = rs(wave if rs.device is None else wave.to(rs.device), torch.tensor([x.size for _, x in group], dtype=torch.int64))
+        res, lens = out["wave"].cpu().numpy(), out["wave_lens"].cpu().numpy()
+        for b, (i, _) in enumerate(group):
+            sigs[i] = np.ascontiguousarray(res[b, :int(lens[b])], dtype=np.float32)
+    return sigs
+
+
+def batches(paths, batch, sample_rate, min_len, log, resample=False, resamplers=None):
     """-> (ids, wave (B, Nmax) fp32 zero padded, lens) per batch of recordings long enough to frame"""
+    resamplers = {} if resamplers is None else resamplers
     for a in range(0, len(paths), batch):
         ids, sigs = [], []
-        for p in paths[a:a + batch]:
-            x = audio.read_wav(p, sample_rate)
+        chunk = paths[a:a + batch]
+        loaded = read_resampled(chunk, sample_rate, resamplers) if resample else None
+        for i, p in enumerate(chunk):
+            x = loaded[i] if resample else audio.read_wav(p, sample_rate)
             if x.size < min_len:
                 log(f"skipped {p}: {x.size} samples, {min_len} needed")
                 continue
@@ -43,16 +81,13 @@ def batches(paths, batch, sample_rate, min_len, log):
             sigs.append(x)
         if not ids:
             continue
-        wave = np.zeros((len(ids), max(s.size for s in sigs)), dtype=np.float32)
-        for b, s in enumerate(sigs):
-            wave[b, :s.size] = s
-        yield ids, wave, [s.size for s in sigs]
+        yield ids, _pad(sigs), [s.size for s in sigs]
 
 
-def global_stats(fe, paths, batch, sample_rate, min_len, log):
+def global_stats(fe, paths, batch, sample_rate, min_len, log, resample=False, resamplers=None):
     total = total_sq = 0.0
     count = 0
-    for _, wave, lens in batches(paths, batch, sample_rate, min_len, log):
+    for _, wave, lens in batches(paths, batch, sample_rate, min_len, log, resample, resamplers):
         out = fe(torch.from_numpy(wave).to(fe.device), torch.tensor(lens, dtype=torch.int64))
         s, q, n = fe.stats(out["melspec"], out["melspec_lens"])
         total, total_sq, count = total + float(s), total_sq + float(q), count + int(n)
@@ -62,7 +97,7 @@ def global_stats(fe, paths, batch, sample_rate, min_len, log):
     return mean, math.sqrt(total_sq / count - mean ** 2 + 1e-8)
 
 
-def run(config, batch=64, sequences=None, stats_path="stats.json", log=print):
+def run(config, batch=64, sequences=None, stats_path="stats.json", log=print, resample=False):
     a = config["audio"]
     out_dir = config["path"]["preprocessed"]
     paths = sorted(glob.glob(os.path.join(config["path"]["data"], "wavs", "*.wav")))
@@ -71,8 +106,9 @@ def run(config, batch=64, sequences=None, stats_path="stats.json", log=print):
     os.makedirs(out_dir, exist_ok=True)
     fe = make_front_end(a)
     min_len = int(a["n_fft"]) // 2 + 1
+    resamplers = {}                                                   # one per distinct native rate, shared by both passes
     if a.get("normalize_mel"):
-        mean, std = global_stats(fe, paths, batch, a["sample_rate"], min_len, lambda m: None)
+        mean, std = global_stats(fe, paths, batch, a["sample_rate"], min_len, lambda m: None, resample, resamplers)
         with open(stats_path, "w", encoding="utf-8") as f:
             json.dump({"mean": mean, "std": std}, f, ensure_ascii=False, indent=2)
         log(f"mean {mean:.6f} std {std:.6f} -> {stats_path}")
@@ -80,7 +116,7 @@ def run(config, batch=64, sequences=None, stats_path="stats.json", log=print):
     if sequences is None:
         log("no --sequences: the files hold `melspec` only; TransformerTTSDataset also needs `transcript` and `sequence`")
     written = 0
-    for ids, wave, lens in batches(paths, batch, a["sample_rate"], min_len, log):
+    for ids, wave, lens in batches(paths, batch, a["sample_rate"], min_len, log, resample, resamplers):
         out = fe(torch.from_numpy(wave).to(fe.device), torch.tensor(lens, dtype=torch.int64))
         mel, mel_lens = out["melspec"].cpu().numpy(), out["melspec_lens"].cpu().numpy()
         for b, name in enumerate(ids):
@@ -104,11 +140,12 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--sequences", default=None)
     ap.add_argument("--stats", default="stats.json")
+    ap.add_argument("--resample", action="store_true", help="bring recordings at another rate to the config's on the device")
     args = ap.parse_args(argv)
     import yaml
     with open(args.config, "r") as f:
         config = yaml.safe_load(f)
-    run(config, batch=args.batch, sequences=args.sequences, stats_path=args.stats)
+    run(config, batch=args.batch, sequences=args.sequences, stats_path=args.stats, resample=args.resample)
 
 
 if __name__ == "__main__":

@@ -2,11 +2,12 @@
 """A `.npz` written by tools/preprocess_mel.py (or a synthesised mel saved the same way) -> a PCM16 `.wav`, through `Vocoder`
 (csrc/vocoder.hip): pseudo-inverse mel basis, then fast Griffin-Lim.
 
-    python tools/vocode_mel.py --config config.yaml --npz FILE.npz [--stats stats.json] --out FILE.wav [--n-iter 32]
+    python tools/vocode_mel.py --config config.yaml --npz FILE.npz [--stats stats.json] --out FILE.wav [--n-iter 32] [--out-rate R]
 
 `melspec` in the file is (n_mels, T) fp32.  With `config['audio']['normalize_mel']` the file holds normalised values and
 `--stats` (the `mean` / `std` file of preprocess_mel.py) is needed to undo that.  The wave has (T - 1) * hop_length samples at
-`config['audio']['sample_rate']`; a mel too short to vocode ((T - 1) * hop_length <= n_fft/2) is refused."""
+`config['audio']['sample_rate']`, or with `--out-rate R` is resampled on the device to R Hz (`audio.Resampler`,
+csrc/resample.hip) before it is written; a mel too short to vocode ((T - 1) * hop_length <= n_fft/2) is refused."""
 import argparse
 import json
 import os
@@ -24,7 +25,11 @@ def make_vocoder(audio_config, mean=None, std=None, **kw):
     return audio.Vocoder(audio_config, mean=mean, std=std, **kw)
 
 
-def run(config, npz_path, out_path, stats_path=None, make_vocoder=make_vocoder, log=print, **kw):
+def make_resampler(orig_rate, new_rate):
+    return audio.Resampler(orig_rate, new_rate)
+
+
+def run(config, npz_path, out_path, stats_path=None, make_vocoder=make_vocoder, log=print, out_rate=None, **kw):
     a = config["audio"]
     mean = std = None
     if a.get("normalize_mel"):
@@ -43,14 +48,18 @@ def run(config, npz_path, out_path, stats_path=None, make_vocoder=make_vocoder, 
         raise ValueError(f"{npz_path}: {T} frames are too few to vocode ((T - 1) * hop_length must exceed n_fft/2 = {n_fft // 2})")
     voc = make_vocoder(a, mean=mean, std=std, **kw)
     out = voc(torch.from_numpy(np.ascontiguousarray(mel.T))[None].to(voc.device), torch.tensor([T], dtype=torch.int64))
+    rate = int(a["sample_rate"])
+    if out_rate is not None and int(out_rate) != rate:
+        out = make_resampler(rate, int(out_rate))(out["wave"], out["wave_lens"])
+        rate = int(out_rate)
     n = int(out["wave_lens"][0])
     wave = out["wave"][0, :n].cpu().numpy()
     peak = float(np.abs(wave).max()) if n else 0.0
     if peak >= 1.0:                                                   # PCM16 clips at full scale
         log(f"peak {peak:.3f}: scaled to 0.99")
         wave = wave * (0.99 / peak)
-    audio.write_wav_pcm16(out_path, wave, int(a["sample_rate"]))
-    log(f"{n} samples ({n / float(a['sample_rate']):.2f} s) -> {out_path}")
+    audio.write_wav_pcm16(out_path, wave, rate)
+    log(f"{n} samples ({n / float(rate):.2f} s) -> {out_path}")
     return n
 
 
@@ -61,11 +70,12 @@ def main(argv=None):
     ap.add_argument("--stats", default=None)
     ap.add_argument("--out", required=True)
     ap.add_argument("--n-iter", type=int, default=32)
+    ap.add_argument("--out-rate", type=int, default=None, help="write the wave at this rate instead of the config's")
     args = ap.parse_args(argv)
     import yaml
     with open(args.config, "r") as f:
         config = yaml.safe_load(f)
-    run(config, args.npz, args.out, stats_path=args.stats, n_iter=args.n_iter)
+    run(config, args.npz, args.out, stats_path=args.stats, n_iter=args.n_iter, out_rate=args.out_rate)
 
 
 if __name__ == "__main__":

@@ -107,6 +107,10 @@ SIGNATURES = {
     "ttts_mel_to_magnitude": (I, [P, L, L, P, I, I, I, I, I, P, P, F, P, P, P]),
     "ttts_istft": (I, [P, P, I, I, I, I, P, P, P, P]),
     "ttts_stft_project": (I, [P, L, P, P, I, I, I, I, P, P, P, F, P, P, P]),
+    "ttts_resample_table_bytes": (Z, [I, I]),
+    "ttts_resample_table_check": (I, [P, Z, I, I, I]),
+    "ttts_resample_tile": (I, []),
+    "ttts_resample": (I, [P, L, P, I, I, I, I, I, P, P, L, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

@@ -23,6 +23,13 @@ The way back is librosa.feature.inverse.mel_to_audio's fast Griffin-Lim, restate
 floor), then spec = magnitude * init, n_iter times { wave = istft(spec); reb = stft(wave); t = reb - momentum / (1 + momentum) *
 prev; prev = reb; spec = magnitude * t / |t| }, wave = istft(spec).  An utterance is vocodable iff (frames - 1) * hop > n_fft/2
 (the front end can reflect what comes back); its wave has (frames - 1) * hop samples, any other row 0 samples.
+
+    rs = Resampler(48000, 22050, device='cuda')                # polyphase Kaiser windowed-sinc table built once (fp64 -> fp32)
+    out = rs(wave, wave_lens)                                  # {'wave': (B, ceil(Nmax L / M)) fp32, 'wave_lens': (B,) int64}
+    samples, rate = read_wav_native(path)                      # a file at its own rate (read_wav refuses another rate)
+
+What `librosa.load(path, sr=...)` does on the way in (csrc/resample.hip): band-limited interpolation, restated from its
+definition (`resample_table`); the output is the front end's input as it is, and the vocoder's output resamples the same way.
 """
 from __future__ import annotations
 
@@ -39,6 +46,8 @@ MAGIC = 0x4C454D54
 HEADER = 8
 SPAN_MULT = 2                                   # vocoder.hip VOCODER_SPAN_MULT: an inverse-STFT workgroup owns SPAN_MULT * n_fft samples
 MAX_MELS = 512                                  # audio_common.h AUDIO_MAX_MELS
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA = 64, 0.9475937167399596, 14.769656459379492   # the 'kaiser_best' design
+RESAMPLE_MAX_L, RESAMPLE_MAX_K, RESAMPLE_MAX_RATIO = 1024, 1280, 8                             # resample.hip RESAMPLE_MAX_*
 
 
 def hz_to_mel(f):
@@ -162,7 +171,17 @@ def denormalize(mel, mean, std):
 
 def read_wav(path: str, sample_rate: int) -> np.ndarray:
     """mono RIFF PCM16 / PCM24 / PCM32 / IEEE float32 -> float32 in [-1, 1); raises if the file's rate is not `sample_rate`
-    (there is no resampler) or it is not mono.  Standard library only."""
+    (nothing is resampled here: `read_wav_native` returns the file's own rate, `Resampler` converts on the device) or it is
+    not mono.  Standard library only."""
+    return _read_wav(path, sample_rate)[0]
+
+
+def read_wav_native(path: str) -> Tuple[np.ndarray, int]:
+    """-> (samples as `read_wav` returns them, the file's sample rate): the same reader without the rate check"""
+    return _read_wav(path, None)
+
+
+def _read_wav(path: str, sample_rate: Optional[int]) -> Tuple[np.ndarray, int]:
     with open(path, "rb") as fh:
         head = fh.read(12)
         if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
@@ -190,19 +209,19 @@ def read_wav(path: str, sample_rate: int) -> np.ndarray:
         code = struct.unpack("<H", fmt[24:26])[0]
     if channels != 1:
         raise ValueError(f"read_wav: {path} has {channels} channels, mono expected")
-    if rate != int(sample_rate):
+    if sample_rate is not None and rate != int(sample_rate):
         raise ValueError(f"read_wav: {path} is sampled at {rate} Hz, {int(sample_rate)} Hz expected (there is no resampler)")
     if code == 1 and bits == 16:
-        return (np.frombuffer(data[:len(data) // 2 * 2], dtype="<i2").astype(np.float32) / np.float32(32768.0))
+        return np.frombuffer(data[:len(data) // 2 * 2], dtype="<i2").astype(np.float32) / np.float32(32768.0), int(rate)
     if code == 1 and bits == 24:
         raw = np.frombuffer(data[:len(data) // 3 * 3], dtype=np.uint8).reshape(-1, 3).astype(np.int32)
         v = raw[:, 0] | (raw[:, 1] << 8) | (raw[:, 2] << 16)
         v = np.where(v >= 1 << 23, v - (1 << 24), v)
-        return (v.astype(np.float64) / float(1 << 23)).astype(np.float32)
+        return (v.astype(np.float64) / float(1 << 23)).astype(np.float32), int(rate)
     if code == 1 and bits == 32:
-        return (np.frombuffer(data[:len(data) // 4 * 4], dtype="<i4").astype(np.float64) / float(1 << 31)).astype(np.float32)
+        return (np.frombuffer(data[:len(data) // 4 * 4], dtype="<i4").astype(np.float64) / float(1 << 31)).astype(np.float32), int(rate)
     if code == 3 and bits == 32:
-        return np.frombuffer(data[:len(data) // 4 * 4], dtype="<f4").astype(np.float32)
+        return np.frombuffer(data[:len(data) // 4 * 4], dtype="<f4").astype(np.float32), int(rate)
     raise ValueError(f"read_wav: {path}: format code {code} with {bits} bits is not PCM16/24/32 or float32")
 
 
@@ -214,6 +233,125 @@ def write_wav_pcm16(path: str, samples: np.ndarray, sample_rate: int) -> None:
         w.setsampwidth(2)
         w.setframerate(int(sample_rate))
         w.writeframes(pcm.tobytes())
+
+
+def bessel_i0(x):
+    """the modified Bessel function I0 by its power series sum_n ((x/2)^2)^n / (n!)^2, in float64 (every term is positive: no
+    cancellation; 60 terms reach 1e-17 of the sum up to |x| = 20 and the loop stops there)"""
+    x = np.asarray(x, dtype=np.float64)
+    y = (x / 2.0) ** 2
+    term = np.ones_like(y)
+    total = np.ones_like(y)
+    for n in range(1, 500):
+        term = term * y / float(n * n)
+        total = total + term
+        if not np.any(term > 1e-17 * total):
+            break
+    return total
+
+
+def resample_ratio(orig_rate: int, new_rate: int) -> Tuple[int, int]:
+    """-> (L, M) = (new, orig) / gcd(orig, new)"""
+    orig, new = int(orig_rate), int(new_rate)
+    if orig < 1 or new < 1 or orig != orig_rate or new != new_rate:
+        raise ValueError(f"resample: the rates must be positive integers (orig_rate {orig_rate}, new_rate {new_rate})")
+    g = math.gcd(orig, new)
+    return new // g, orig // g
+
+
+def resample_table(orig_rate: int, new_rate: int, zeros: int = RESAMPLE_ZEROS, rolloff: float = RESAMPLE_ROLLOFF,
+                   beta: float = RESAMPLE_BETA) -> Tuple[np.ndarray, int, int, int]:
+    """-> (table fp32 (K, L) C-contiguous, L, M, K): the polyphase weights of csrc/resample.hip, tap-major (table[k, r] is
+    tap k of phase r = j mod L), built in float64 and rounded to fp32 once.  s = rolloff * min(1, L / M), W = ceil(zeros / s),
+    K = 2 W + 2, h[r][k] = s * kernel(s * ((W - k) + ((r M) mod L) / L)), kernel(u) = sinc(u) * I0(beta sqrt(1 - (u / zeros)^2)) /
+    I0(beta) inside |u| < zeros and exactly 0 outside."""
+    L, M = resample_ratio(orig_rate, new_rate)
+    if L == M:
+        raise ValueError(f"resample_table: the two rates are equal ({orig_rate}): there is nothing to interpolate")
+    zeros = int(zeros)
+    if zeros < 1 or not 0.0 < rolloff <= 1.0 or not beta >= 0.0:
+        raise ValueError(f"resample_table: need zeros >= 1, 0 < rolloff <= 1 and beta >= 0 (zeros {zeros}, rolloff {rolloff}, "
+                         f"beta {beta})")
+    s = float(rolloff) * min(1.0, L / M)
+    W = int(math.ceil(zeros / s))
+    K = 2 * W + 2
+    if L > RESAMPLE_MAX_L or K > RESAMPLE_MAX_K or max(L, M) > RESAMPLE_MAX_RATIO * min(L, M):
+        raise ValueError(f"resample_table: {orig_rate} -> {new_rate} Hz needs L {L}, M {M}, K {K}; the kernel takes L <= "
+                         f"{RESAMPLE_MAX_L}, K <= {RESAMPLE_MAX_K} and rates within a factor of {RESAMPLE_MAX_RATIO}")
+    frac = ((np.arange(L, dtype=np.int64) * M) % L).astype(np.float64) / L
+    u = s * ((W - np.arange(K, dtype=np.float64))[:, None] + frac[None, :])               # (K, L)
+    v = u / zeros
+    inside = np.abs(v) < 1.0
+    window = np.where(inside, bessel_i0(beta * np.sqrt(np.where(inside, 1.0 - v * v, 0.0))) / bessel_i0(beta), 0.0)
+    return np.ascontiguousarray((s * np.sinc(u) * window).astype(np.float32)), L, M, K
+
+
+class Resampler:
+    """Band-limited (Kaiser windowed-sinc, polyphase) resampling of a ragged batch on the device: one launch of csrc/resample.hip
+    a call, nothing read back, capturable into a HIP graph.
+
+        rs = Resampler(16000, 22050, device='cuda')        # table built once (fp64 -> fp32) and uploaded
+        out = rs(wave, wave_lens)                          # {'wave': (B, ceil(Nmax L / M)) fp32, 'wave_lens': (B,) int64}
+        mel = MelFrontEnd(cfg)(**out)                      # the output is the front end's input as it is
+
+    Output j sits at input time j M / L (L / M = new / orig in lowest terms); a row of len samples gives ceil(len L / M), the
+    rest of its row zeros; samples at or behind a length are never read.  Equal rates: no launch, the input tensor comes back
+    with its lengths clamped to [0, Nmax]."""
+
+    def __init__(self, orig_rate: int, new_rate: int, device=None, zeros: int = RESAMPLE_ZEROS, rolloff: float = RESAMPLE_ROLLOFF,
+                 beta: float = RESAMPLE_BETA):
+        import torch
+        self.orig_rate, self.new_rate = int(orig_rate), int(new_rate)
+        self.L, self.M = resample_ratio(orig_rate, new_rate)
+        self.K, self.table_host, self.table = 0, None, None
+        if self.L == self.M:                               # the identity needs neither a table nor the library
+            self.device = torch.device(device) if device is not None else None
+            return
+        from . import _lib
+        self.table_host, _, _, self.K = resample_table(orig_rate, new_rate, zeros, rolloff, beta)
+        lib = _lib.load()
+        if lib.ttts_resample_table_bytes(self.L, self.K) != self.table_host.nbytes:
+            raise RuntimeError("Resampler: the table layout disagrees with the library")
+        _lib.check(lib.ttts_resample_table_check(self.table_host.ctypes.data, self.table_host.nbytes, self.L, self.M, self.K),
+                   "ttts_resample_table_check")
+        if not torch.cuda.is_available():
+            raise RuntimeError("Resampler needs the HIP device (no CPU fallback)")
+        self.device = torch.device(device if device is not None else "cuda")
+        self.table = torch.from_numpy(self.table_host).to(self.device)
+
+    def out_len(self, n: int) -> int:
+        """samples a row of n samples comes back with: ceil(n L / M)"""
+        return -((-int(n) * self.L) // self.M)
+
+    def __call__(self, wave, wave_lens):
+        import torch
+        if wave.dim() != 2 or min(wave.shape) < 1:
+            raise ValueError(f"Resampler: wave must be (B, Nmax), got {tuple(wave.shape)}")
+        B, Nmax = wave.shape
+        if tuple(wave_lens.shape) != (B,):
+            raise ValueError(f"Resampler.wave_lens must have shape ({B},), got {tuple(wave_lens.shape)}")
+        identity = self.L == self.M
+        if not wave.is_cuda and not identity:
+            raise ValueError(f"Resampler.wave: expected a CUDA/HIP tensor (the HIP path has no CPU fallback), got {wave.device}")
+        if wave.dtype != torch.float32:
+            raise ValueError(f"Resampler.wave: expected dtype {torch.float32}, got {wave.dtype}")
+        if wave_lens.dtype.is_floating_point or wave_lens.dtype == torch.bool:
+            raise ValueError(f"Resampler.wave_lens must be integers, got {wave_lens.dtype}")
+        lens = wave_lens.to(wave.device).to(torch.int64).contiguous()
+        if identity:
+            return {"wave": wave, "wave_lens": lens.clamp(0, Nmax)}
+        from . import _lib
+        from .ops import _p, _stream
+        wave = wave.detach()
+        if (Nmax > 1 and wave.stride(1) != 1) or (B > 1 and wave.stride(0) < Nmax):
+            wave = wave.contiguous()
+        ld = wave.stride(0) if B > 1 else Nmax
+        Nout = self.out_len(Nmax)
+        out = torch.empty(B, Nout, dtype=torch.float32, device=wave.device)
+        out_lens = torch.empty(B, dtype=torch.int64, device=wave.device)
+        _lib.check(_lib.load().ttts_resample(_p(wave), ld, _p(lens), B, Nmax, self.L, self.M, self.K, _p(self.table), _p(out), Nout,
+                                             _p(out_lens), _stream()), "ttts_resample")
+        return {"wave": out, "wave_lens": out_lens}
 
 
 class MelFrontEnd:
