@@ -49,7 +49,7 @@ for i in range(6):
                         return k
             return None
         print("lossB in", where(tsB._cur.losses["full"]), "lossA in", where(tsA._cur.losses["full"]) if tsA._cur.graphs else None,
-              "arena in", where(ops._amax_arenas[torch.device("cuda", 0)].buf), "B planes.dev in", where(tsB._planes.dev), flush=True)
+              "arena in", where(ops._amax_arenas[torch.device("cuda", 0)].buf), "B planes.dev in", where(tsB._planes.table.dev), flush=True)
     if i == 3 and "D" in mode:
         if "1" not in mode:
             del tsA, lmA, optA, schA

@@ -590,13 +590,9 @@ def bump_param_epoch() -> None:
     _param_epoch += 1
 
 
-class _PlaneEntry:
-    __slots__ = ("wref", "off", "mode", "rows", "cols", "c2", "taps", "planes", "tag")
-
-
 _BATCHED_SPLIT = True
 _plane_entries: list = []        # every (weight, mode) split so far, for the one-launch refresh after an optimizer step
-_plane_tables: dict = {}         # flat-storage address -> (signature, device descriptor table, pinned host copy, total blocks)
+_plane_tables: dict = {}         # flat-storage address -> the _SplitTable of that model's last process-wide refresh
 
 
 # Weight-image modes of ttts_weight_split (the table of include/ttts_hip.h): which matrix of a weight is laid out, and for
@@ -607,11 +603,94 @@ H3_LIN_FWD, H3_LIN_BWD, H3_CONV_FWD, H3_CONV_BWD = 4, 5, 6, 7      # fp16x3: two
 H3D_LIN_FWD, H3D_LIN_BWD = 8, 9                                    # fp16x3 for the LDS-DMA kernels (h3d / h3i / h3d_img)
 
 
-def _split_units(rows: int, cols: int, mode: int, c2: int) -> int:
-    """work units of one entry of the batched refresh; a LINEAR entry's c2 / taps may hold the geometry of a stacked image
-    (64-bit packed, `_StackedPlanes`), which is no part of the count"""
-    conv = mode in (X6_CONV_FWD, X6_CONV_BWD, H3_CONV_FWD, H3_CONV_BWD)
-    return int(_lib.load().ttts_weight_split_units(rows, cols, mode, c2 if conv else 0))
+_CONV_MODES = (X6_CONV_FWD, X6_CONV_BWD, H3_CONV_FWD, H3_CONV_BWD)
+
+
+def _pack2(hi: int, lo: int) -> int:
+    return (int(hi) << 32) | int(lo)
+
+
+class _PlaneEntry:
+    """One weight image: the `rows` x `cols` matrix that `mode` makes of the numbers `off` bytes into the parameter `wref()`
+    (the holder: the entry hangs in its `_ttts_planes` dict), laid out in `planes` (at address `image`); `units` work units of a
+    batched refresh.
+    What `c2` / `taps` hold, as ttts_weight_split and a row of ttts_weight_split_batched read them:
+      plain   0, 0
+      conv    (the conv modes) the weight's other channel count and its taps: cols = taps * c2
+      window  (linear modes, `_StackedPlanes`) the entry is a rows x cols window of an image it shares with other entries:
+              _pack2(image rows, image cols), _pack2(the window's first row, first column); no part of `units`
+    `tag` names the state of the holder the image was last written for: (version counter, source address, parameter epoch),
+    an epoch of -1 being none.  Only the methods below build it or take it apart."""
+    __slots__ = ("wref", "off", "mode", "rows", "cols", "c2", "taps", "planes", "image", "units", "tag")
+
+    def source(self, holder) -> int:
+        return holder.data_ptr() + self.off
+
+    def where(self, holder):
+        """what a descriptor row, and so a graph that recorded its table, depends on"""
+        return (holder.data_ptr() + self.off, self.image, holder._version)
+
+    def current(self, holder) -> bool:
+        return self.tag == (holder._version, holder.data_ptr() + self.off, _param_epoch)
+
+    def epoch_behind(self) -> bool:
+        return self.tag[2] != _param_epoch
+
+    def only_epoch_moved(self, holder) -> bool:
+        """an optimizer stepped through raw pointers and nothing else happened: what a batched refresh may serve"""
+        version, source, epoch = self.tag
+        return epoch != _param_epoch and version == holder._version and source == holder.data_ptr() + self.off
+
+    def mark_current(self, holder=None) -> None:
+        """holder None: only the epoch was behind (`only_epoch_moved`) and a refresh has just written the image"""
+        self.tag = (holder._version, holder.data_ptr() + self.off, _param_epoch) if holder is not None else self.tag[:2] + (_param_epoch,)
+
+    def mark_stale(self) -> None:
+        self.tag = (self.tag[0], self.tag[1], -1)
+
+    def row(self, holder, first_unit: int) -> list:
+        return [holder.data_ptr() + self.off, self.image, self.rows, self.cols, self.mode, self.c2, self.taps, first_unit]
+
+
+def _register_planes(ent, w: torch.Tensor, key, mode: int, rows: int, cols: int, c2: int, taps: int, planes: torch.Tensor):
+    """Fill `ent`, or with None a new entry hung under `key` on the parameter `w` is (a `param_rows` slice of), for an image
+    of `w` in `planes`; -> (holder, entry), marked current: a caller that has not written the image yet marks it stale."""
+    holder, sub = getattr(w, "_ttts_planes_owner", None) or (w, 0)
+    if ent is None:
+        cache = getattr(holder, "_ttts_planes", None)
+        if cache is None:
+            cache = holder._ttts_planes = {}
+        ent = cache[(key, sub)] = _PlaneEntry()
+        ent.wref = weakref.ref(holder)
+        _plane_entries.append(ent)
+    ent.off = w.data_ptr() - holder.data_ptr()
+    ent.mode, ent.rows, ent.cols, ent.c2, ent.taps, ent.planes, ent.image = mode, rows, cols, c2, taps, planes, planes.data_ptr()
+    ent.units = int(_lib.load().ttts_weight_split_units(rows, cols, mode, c2 if mode in _CONV_MODES else 0))
+    ent.mark_current(holder)
+    return holder, ent
+
+
+class _SplitTable:
+    """The descriptor table of one ttts_weight_split_batched launch over `pairs` of (holder, entry): its rows, their
+    page-locked host tensor (the upload does not synchronise, and reads it after this returns: it lives as long as the device
+    copy), the device copy and the launch's total work units."""
+
+    def __init__(self, pairs):
+        self.rows, self.units = self.layout(pairs)
+        self.host = torch.tensor(self.rows, dtype=torch.int64).pin_memory()
+        self.dev = self.host.to(pairs[0][1].planes.device, non_blocking=True)
+
+    @staticmethod
+    def layout(pairs):
+        rows, units = [], 0
+        for holder, e in pairs:
+            rows.append(e.row(holder, units))
+            units += e.units
+        return rows, units
+
+    def launch(self) -> None:
+        _lib.check(_lib.load().ttts_weight_split_batched(_p(self.dev), len(self.rows), self.units, _stream()),
+                   "ttts_weight_split_batched")
 
 
 def _refresh_all_planes(storage: int) -> None:
@@ -620,37 +699,27 @@ def _refresh_all_planes(storage: int) -> None:
     through raw pointers) with ONE launch instead of one per weight and mode.  Weights of other models are left alone:
     their owners may be using them on another stream."""
     global _plane_entries
-    live, mine, sig = [], [], []
+    live, pairs, storages = [], [], set()
     for e in _plane_entries:
         w = e.wref()
         if w is None:
             continue
         live.append(e)
-        if w.untyped_storage().data_ptr() != storage:
-            continue
-        mine.append(e)
-        if e.tag[0] == w._version and e.tag[1] == w.data_ptr() + e.off and e.tag[2] != _param_epoch:
-            sig.append((e.tag[1], e.planes.data_ptr(), e.rows, e.cols, e.mode, e.c2, e.taps))
+        at = w.untyped_storage().data_ptr()
+        storages.add(at)
+        if at == storage and e.only_epoch_moved(w):
+            pairs.append((w, e))
     _plane_entries = live
-    for k in [k for k in _plane_tables if not any(e.wref() is not None and e.wref().untyped_storage().data_ptr() == k for e in live)]:
+    for k in [k for k in _plane_tables if k not in storages]:
         del _plane_tables[k]
-    if not sig:
+    if not pairs:
         return
-    sig_t = tuple(sig)
     table = _plane_tables.get(storage)
-    if table is None or table[0] != sig_t:
-        rows, blk = [], 0
-        for s in sig:
-            rows.append(list(s) + [blk])
-            blk += _split_units(s[2], s[3], s[4], s[5])
-        host = torch.tensor(rows, dtype=torch.int64).pin_memory()      # page-locked: the upload does not synchronise
-        table = _plane_tables[storage] = (sig_t, host.to(mine[0].planes.device, non_blocking=True), host, blk)
-    lib = _lib.load()
-    _lib.check(lib.ttts_weight_split_batched(_p(table[1]), len(sig), table[3], _stream()), "ttts_weight_split_batched")
-    refreshed = {s[1] for s in sig}
-    for e in mine:
-        if e.planes.data_ptr() in refreshed:
-            e.tag = (e.tag[0], e.tag[1], _param_epoch)
+    if table is None or table.rows != _SplitTable.layout(pairs)[0]:
+        table = _plane_tables[storage] = _SplitTable(pairs)
+    table.launch()
+    for _, e in pairs:
+        e.mark_current()
 
 
 class PlaneTable:
@@ -671,42 +740,31 @@ class PlaneTable:
                     self.entries.append((prm, ent))
         if not self.entries:
             raise RuntimeError("PlaneTable: the module has no weight planes yet (run one forward + backward first)")
-        rows, blk = [], 0
-        self.sig = []
-        for prm, e in self.entries:
-            src = prm.data_ptr() + e.off
-            self.sig.append((src, e.planes.data_ptr(), prm._version))
-            rows.append([src, e.planes.data_ptr(), e.rows, e.cols, e.mode, e.c2, e.taps, blk])
-            blk += _split_units(e.rows, e.cols, e.mode, e.c2)
-        self.blocks = blk
-        self.host = torch.tensor(rows, dtype=torch.int64).pin_memory()
-        self.dev = self.host.to(self.entries[0][1].planes.device, non_blocking=True)
+        self.sig = [e.where(prm) for prm, e in self.entries]
+        self.table = _SplitTable(self.entries)
 
     def valid(self) -> bool:
         """The parameters still live where the table says (no `.to()`, no re-allocated planes, no in-place autograd edit)."""
-        return all((prm.data_ptr() + e.off, e.planes.data_ptr(), prm._version) == sg
-                   for (prm, e), sg in zip(self.entries, self.sig))
+        return all(e.where(prm) == sg for (prm, e), sg in zip(self.entries, self.sig))
 
     def stale(self) -> bool:
-        return any(e.tag[2] != _param_epoch for _, e in self.entries)
+        return any(e.epoch_behind() for _, e in self.entries)
 
     def refresh(self) -> None:
         """Re-split every weight of the module with one batched launch sequence and mark the planes current."""
-        _lib.check(_lib.load().ttts_weight_split_batched(_p(self.dev), len(self.entries), self.blocks, _stream()),
-                   "ttts_weight_split_batched")
-        for prm, e in self.entries:
-            e.tag = (prm._version, prm.data_ptr() + e.off, _param_epoch)
+        self.table.launch()
+        self.mark_current()
 
     def mark_current(self) -> None:
         """Before capturing a micro-batch that does NOT begin an accumulation window: the window's first graph refreshes the
         planes when it replays, so the launches recorded here must use them as they are (no per-weight re-split nodes)."""
         for prm, e in self.entries:
-            e.tag = (prm._version, prm.data_ptr() + e.off, _param_epoch)
+            e.mark_current(prm)
 
     def mark_stale(self) -> None:
         """After a capture: the recorded refresh has not run, so the host must not believe the planes are current."""
         for _, e in self.entries:
-            e.tag = (e.tag[0], e.tag[1], -1)
+            e.mark_stale()
 
 
 def _planes(w: torch.Tensor, mode: int, rows: int, cols: int, c2: int = 0, taps: int = 0) -> torch.Tensor:
@@ -717,16 +775,14 @@ def _planes(w: torch.Tensor, mode: int, rows: int, cols: int, c2: int = 0, taps:
     owner = getattr(w, "_ttts_planes_owner", None)
     holder, sub = owner if owner is not None else (w, 0)
     cache = getattr(holder, "_ttts_planes", None)
-    tag = (holder._version, w.data_ptr(), _param_epoch)
-    key = (mode, sub)
-    ent = cache.get(key) if cache is not None else None
+    ent = cache.get((mode, sub)) if cache is not None else None
     if ent is not None:
-        if ent.tag == tag:
+        if ent.current(holder):
             return ent.planes
-        if _BATCHED_SPLIT and ent.tag[0] == tag[0] and ent.tag[1] == tag[1] and not torch.cuda.is_current_stream_capturing():
-            _refresh_all_planes(holder.untyped_storage().data_ptr())   # only the epoch moved: refresh this model at once (never inside a capture:
+        if _BATCHED_SPLIT and ent.only_epoch_moved(holder) and not torch.cuda.is_current_stream_capturing():
+            _refresh_all_planes(holder.untyped_storage().data_ptr())   # refresh this model at once (never inside a capture:
             #                                       the process-wide table is not owned by the graph, see PlaneTable)
-            if ent.tag == tag:
+            if ent.current(holder):
                 return ent.planes
     lib = _lib.load()
     nwords = (int(lib.ttts_split_image_bytes(rows, cols, mode, c2, taps)) + 1) // 2      # (fp16x3 images pad channels to 32)
@@ -737,19 +793,7 @@ def _planes(w: torch.Tensor, mode: int, rows: int, cols: int, c2: int = 0, taps:
     else:
         planes = ent.planes
     _lib.check(lib.ttts_weight_split(_p(w), _p(planes), rows, cols, mode, c2, taps, _stream()), "ttts_weight_split")
-    try:
-        if cache is None:
-            cache = {}
-            holder._ttts_planes = cache
-        if ent is None:
-            ent = _PlaneEntry()
-            ent.wref = weakref.ref(holder)
-            _plane_entries.append(ent)
-            cache[key] = ent
-        ent.off = w.data_ptr() - holder.data_ptr()
-        ent.mode, ent.rows, ent.cols, ent.c2, ent.taps, ent.planes, ent.tag = mode, rows, cols, c2, taps, planes, tag
-    except (AttributeError, TypeError):
-        pass
+    _register_planes(ent, w, mode, mode, rows, cols, c2, taps, planes)
     return planes
 
 
@@ -1240,10 +1284,6 @@ def linear(x, w, b=None, residual=None, act=ACT_NONE, drop_p=0.0, seed=0, row_sh
 
 
 # ----------------------------------------------------------------------------------------------- fused cross-attention K/V
-def _pack2(hi: int, lo: int) -> int:
-    return (int(hi) << 32) | int(lo)
-
-
 class _StackedPlanes:
     """ONE fp16x3 weight image of several parameter row slices (all (rows, cols)) STACKED: along the image's rows for the forward
     image (H3D_LIN_FWD: the slices' output columns side by side, N = n * rows) or along its reduction index for the data-gradient
@@ -1254,63 +1294,42 @@ class _StackedPlanes:
     captured graph replays cover them like any other weight."""
 
     def __init__(self, slices, mode: int):
-        lib = _lib.load()
-        self.mode, self.n = mode, len(slices)
+        n = len(slices)
         rows, cols = slices[0].shape
-        self.rows, self.cols = rows, cols
         if mode in (H3_LIN_FWD, H3D_LIN_FWD):
-            self.Rimg, self.Cimg = self.n * rows, cols          # forward image: (n rows, cols)
-            wins = [(_pack2(self.Rimg, self.Cimg), _pack2(i * rows, 0), rows, cols) for i in range(self.n)]
+            image = (n * rows, cols)                            # forward image: (n rows, cols)
+            wins = [(_pack2(i * rows, 0), rows, cols) for i in range(n)]
         else:
             if rows % 32 != 0:
                 raise ValueError("stacked data-gradient image: the slices' row counts must be multiples of 32")
-            self.Rimg, self.Cimg = cols, self.n * rows          # image of w^T: (cols, n rows)
-            wins = [(_pack2(self.Rimg, self.Cimg), _pack2(0, i * rows), cols, rows) for i in range(self.n)]
-        nwords = (int(lib.ttts_split_image_bytes(self.Rimg, self.Cimg, mode, 0, 0)) + 1) // 2
+            image = (cols, n * rows)                            # image of w^T: (cols, n rows)
+            wins = [(_pack2(0, i * rows), cols, rows) for i in range(n)]
+        nwords = (int(_lib.load().ttts_split_image_bytes(*image, mode, 0, 0)) + 1) // 2
         self.planes = torch.empty(nwords, dtype=torch.int16, device=slices[0].device)
         self.entries = []
         key = ("stack", mode, tuple(id(getattr(sl, "_ttts_planes_owner", (sl, 0))[0]) for sl in slices))
-        for sl, (geo, off, R, C) in zip(slices, wins):
-            holder, sub = getattr(sl, "_ttts_planes_owner", (sl, 0))
-            cache = getattr(holder, "_ttts_planes", None)
-            if cache is None:
-                cache = {}
-                holder._ttts_planes = cache
-            ent = _PlaneEntry()
-            ent.wref = weakref.ref(holder)
-            ent.off = sl.data_ptr() - holder.data_ptr()
-            ent.mode, ent.rows, ent.cols, ent.c2, ent.taps, ent.planes = mode, R, C, geo, off, self.planes
-            ent.tag = (holder._version, sl.data_ptr(), -1)
-            cache[(key, sub)] = ent
-            _plane_entries.append(ent)
+        for sl, (first, R, C) in zip(slices, wins):
+            holder, ent = _register_planes(None, sl, key, mode, R, C, _pack2(*image), first, self.planes)
+            ent.mark_stale()                                    # (nothing is written yet: `get` does that)
             self.entries.append((holder, ent))
         # its own small refresh table (first build, and whenever the process-wide / TrainStep refresh has not covered it)
-        tab, blk = [], 0
-        for holder, e in self.entries:
-            tab.append([holder.data_ptr() + e.off, self.planes.data_ptr(), e.rows, e.cols, e.mode, e.c2, e.taps, blk])
-            blk += _split_units(e.rows, e.cols, e.mode, 0)
-        self.blocks = blk
-        self.sig = [(holder.data_ptr() + e.off) for holder, e in self.entries]
-        self.table = torch.tensor(tab, dtype=torch.int64).to(self.planes.device)
+        self.table = _SplitTable(self.entries)
 
     def alive(self, slices) -> bool:
-        return len(slices) == self.n and all(h.data_ptr() + e.off == sl.data_ptr() and e.planes is self.planes
-                                             for (h, e), sl in zip(self.entries, slices))
+        return len(slices) == len(self.entries) and all(e.source(h) == sl.data_ptr() for (h, e), sl in zip(self.entries, slices))
 
     def current(self) -> bool:
-        return all(e.tag == (h._version, h.data_ptr() + e.off, _param_epoch) for h, e in self.entries)
+        return all(e.current(h) for h, e in self.entries)
 
     def get(self) -> torch.Tensor:
         if not self.current():
-            h0 = self.entries[0][0]
-            only_epoch = all(e.tag[0] == h._version and e.tag[1] == h.data_ptr() + e.off for h, e in self.entries)
+            only_epoch = all(e.current(h) or e.only_epoch_moved(h) for h, e in self.entries)
             if _BATCHED_SPLIT and only_epoch and not torch.cuda.is_current_stream_capturing():
-                _refresh_all_planes(h0.untyped_storage().data_ptr())       # the optimizer stepped: this model's images at once
+                _refresh_all_planes(self.entries[0][0].untyped_storage().data_ptr())   # the optimizer stepped: this model's images at once
             if not self.current():
-                _lib.check(_lib.load().ttts_weight_split_batched(_p(self.table), self.n, self.blocks, _stream()),
-                           "ttts_weight_split_batched (stacked image)")
+                self.table.launch()
                 for h, e in self.entries:
-                    e.tag = (h._version, h.data_ptr() + e.off, _param_epoch)
+                    e.mark_current(h)
         return self.planes
 
 
