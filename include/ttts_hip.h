@@ -702,6 +702,48 @@ int ttts_resample_table_check(const void* host_table, size_t bytes, int L, int M
 int ttts_resample_tile(void);
 int ttts_resample(const float* wave, int64_t ld_batch, const int64_t* wave_lens, int B, int Nmax, int L, int M, int K,
                   const float* table, float* out, int64_t ld_out, int64_t* out_lens, void* stream);
+/* ---- Frame pitch and energy: YIN F0, voicing, aperiodicity and the STFT frame energy of a ragged batch of waveforms, and the
+ * phoneme-level means of such frame values (pitch.hip; additive, the ABI version stays 24).  YIN restated from its definition.
+ *   framing     the front end's: pitch frame t of utterance b holds x_n = wave[g], g = t * hop - F/2 + n, n < F = frame_length;
+ *               g < 0 reads -g, g >= len_b reads 2 (len_b - 1) - g.  len_b = wave_lens[b] clamped to [0, Nmax]; frames_b =
+ *               1 + len_b / hop, or 0 when len_b <= max(F, n_fft) / 2 (written to `frames`, int64); the outputs are (B, Tmax) with
+ *               Tmax = 1 + Nmax / hop, rows at or beyond frames_b zeros.  Samples at or beyond len_b are never read.
+ *   difference  d(tau) = sum_{j < W} (x_j - x_{j+tau})^2 for tau = 1 .. tau_max, W = window, differences squared in fp32 -- never
+ *               e(0) + e(tau) - 2 acf(tau).  Summed over blocks of BL samples (ascending j, fused multiply-adds from 0 inside a
+ *               block), the block partials added in ascending order; BL = ttts_pitch_block(...): hop when hop divides W, W / hop <= 8
+ *               and the shared partials fit the workgroup's LDS, else W.
+ *   normalised  d'(tau) = d(tau) * tau / sum_{k <= tau} d(k); 1 where that running sum is 0 (a silent frame)
+ *   lag         tau_0 = the first tau in [tau_min, tau_max] with d'(tau) < threshold.  With one the frame is voiced and tau* is
+ *               reached from tau_0 by stepping up while tau + 1 <= tau_max and d'(tau + 1) < d'(tau); without one it is unvoiced
+ *               and tau* is the first argmin of d' over [tau_min, tau_max].
+ *   outputs     voiced (uint8, 0 / 1); aperiodicity = d'(tau*); f0 = sample_rate / (tau* + s) when voiced, exactly 0 otherwise;
+ *               s = clamp(0.5 (a - c) / (a - 2 b + c), -0.5, 0.5) with a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1) when
+ *               tau_min < tau* < tau_max and a - 2 b + c > 0, else 0
+ *   energy      sqrt(sum_{k = 0 .. n_fft/2} |X[k]|^2) with X the front end's STFT of the n_fft samples centred at t * hop, from
+ *               y_n = hann[n] * x_n as (n_fft * sum y^2 + (sum y)^2 + (sum (-1)^n y)^2) / 2; `hann` is the front end's window:
+ *               n_fft floats, the periodic Hann of win_length zero-padded and centred
+ *   means       ttts_segment_mean: phoneme p < phoneme_lens[b] of utterance b covers frames [c_p, c_p + dur_p), c the exclusive
+ *               prefix sum of durations[b, :] ((B, Pmax) int64, negative counts as 0), clipped to frames[b] (clamped to [0, Tmax]);
+ *               mean[b, p] = the fp32 sum of values[b, t] over those frames (those with mask[b, t] != 0 when a mask is given) in
+ *               ascending t, divided by their number counts[b, p] (int32); 0 when none counts; phonemes at or beyond
+ *               phoneme_lens[b] get 0 and 0.  values is (B, Tmax) fp32 at stride ld_values, mask (B, Tmax) uint8 at ld_mask.
+ * ttts_pitch_energy is one launch over the ragged batch, a workgroup per ttts_pitch_frames(...) consecutive frames of an
+ * utterance, ttts_pitch_block(...) the block length BL of its sums (both 0 for a shape the entry refuses); ttts_pitch_lags is the number of neighbouring lags a thread carries (a build constant, for the benchmark's
+ * label).  ttts_segment_mean is one launch, a wave per utterance.  No host read, no allocation, no atomics, the same bits
+ * whatever the grid, the batch or the call, capturable into a HIP graph.  Refused before any launch, with a message that names
+ * the value: null pointers (mask may be NULL), B < 1 or B > 65535 (the grid), Nmax < 1 or Nmax > 2^30, n_fft not in {256, 512,
+ * 1024, 2048}, win_length outside [1, n_fft], frame_length odd, < 2 or > 4096, hop < 1 or hop > frame_length, window < 1,
+ * tau_min < 2, tau_min >= tau_max, window + tau_max > frame_length, threshold outside (0, 1), sample_rate <= 0, Tmax or Pmax
+ * < 1, strides that do not cover a row, misaligned pointers (4 bytes; 8 for the int64 arrays). */
+int ttts_pitch_lags(void);
+int ttts_pitch_frames(int n_fft, int hop, int frame_length, int window, int tau_max);
+int ttts_pitch_block(int n_fft, int hop, int frame_length, int window, int tau_max);
+int ttts_pitch_energy(const float* wave, int64_t ld_batch, const int64_t* wave_lens, int B, int Nmax, int n_fft, int win_length, int hop,
+                      int frame_length, int window, int tau_min, int tau_max, float sample_rate, float threshold, const float* hann,
+                      float* f0, uint8_t* voiced, float* aperiodicity, float* energy, int64_t* frames, void* stream);
+int ttts_segment_mean(const float* values, int64_t ld_values, const int64_t* durations, const int64_t* phoneme_lens,
+                      const int64_t* frames, const uint8_t* mask, int64_t ld_mask, int B, int Tmax, int Pmax, float* mean,
+                      int32_t* counts, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

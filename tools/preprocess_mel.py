@@ -2,7 +2,7 @@
 """A directory of recordings -> the `.npz` files `TransformerTTSDataset` trains from (the mel half of the reference's
 `preprocess.py:28-72`), through `MelFrontEnd` (csrc/audio.hip).
 
-    python tools/preprocess_mel.py --config config.yaml [--batch 64] [--sequences DIR] [--stats stats.json] [--resample]
+    python tools/preprocess_mel.py --config config.yaml [--batch 64] [--sequences DIR] [--stats stats.json] [--resample] [--prosody]
 
 Reads `config['path']['data']/wavs/*.wav` (mono; at `config['audio']['sample_rate']`, or with `--resample` at any rate: the
 recordings of a batch that are at another rate are grouped by their rate and brought to the config's on the device by
@@ -12,7 +12,10 @@ batches adds sum, sum of squares and count of the unnormalised log-mels, mean = 
 to the `--stats` file with the keys `mean` and `std`; the second pass writes `melspec (n_mels, T)` fp32, normalised with them.
 Phonemisation is not done here (it needs `g2p_en`): `--sequences DIR` copies `transcript`, `phoneme` and `sequence` from the
 `<id>.npz` of DIR (files written by the reference's preprocess.py); without it only `melspec` is written, which the data set
-cannot train from yet, and the tool says so.  A recording of n_fft/2 samples or fewer cannot be framed and is skipped."""
+cannot train from yet, and the tool says so.  A recording of n_fft/2 samples or fewer cannot be framed and is skipped.
+`--prosody` adds the frame-level targets of a FastSpeech-2-style student to each file, from `audio.PitchEnergy` (csrc/pitch.hip) on
+the same uploaded batch and the front end's window table: `f0` (fp32, Hz, 0 where unvoiced), `voiced` (bool) and `energy` (fp32),
+each cut to the utterance's frames (the columns of `melspec`)."""
 import argparse
 import glob
 import json
@@ -34,6 +37,10 @@ def make_front_end(audio_config):
 
 def make_resampler(orig_rate, new_rate):
     return audio.Resampler(orig_rate, new_rate)
+
+
+def make_pitch_energy(audio_config, front_end):
+    return audio.PitchEnergy(audio_config, front_end=front_end)
 
 
 def _pad(sigs):
@@ -97,7 +104,7 @@ def global_stats(fe, paths, batch, sample_rate, min_len, log, resample=False, re
     return mean, math.sqrt(total_sq / count - mean ** 2 + 1e-8)
 
 
-def run(config, batch=64, sequences=None, stats_path="stats.json", log=print, resample=False):
+def run(config, batch=64, sequences=None, stats_path="stats.json", log=print, resample=False, prosody=False):
     a = config["audio"]
     out_dir = config["path"]["preprocessed"]
     paths = sorted(glob.glob(os.path.join(config["path"]["data"], "wavs", "*.wav")))
@@ -115,12 +122,21 @@ def run(config, batch=64, sequences=None, stats_path="stats.json", log=print, re
         fe.set_stats(mean, std)
     if sequences is None:
         log("no --sequences: the files hold `melspec` only; TransformerTTSDataset also needs `transcript` and `sequence`")
+    pe = make_pitch_energy(a, fe) if prosody else None
     written = 0
     for ids, wave, lens in batches(paths, batch, a["sample_rate"], min_len, log, resample, resamplers):
-        out = fe(torch.from_numpy(wave).to(fe.device), torch.tensor(lens, dtype=torch.int64))
+        wave_dev, lens_host = torch.from_numpy(wave).to(fe.device), torch.tensor(lens, dtype=torch.int64)
+        out = fe(wave_dev, lens_host)
         mel, mel_lens = out["melspec"].cpu().numpy(), out["melspec_lens"].cpu().numpy()
+        if prosody:
+            pro = {k: v.cpu().numpy() for k, v in pe(wave_dev, lens_host).items()}
         for b, name in enumerate(ids):
             fields = {"melspec": np.ascontiguousarray(mel[b, :int(mel_lens[b])].T, dtype=np.float32)}
+            if prosody:
+                n = min(int(pro["frames"][b]), int(mel_lens[b]))
+                fields.update(f0=np.ascontiguousarray(pro["f0"][b, :n], dtype=np.float32),
+                              voiced=np.ascontiguousarray(pro["voiced"][b, :n], dtype=np.bool_),
+                              energy=np.ascontiguousarray(pro["energy"][b, :n], dtype=np.float32))
             if sequences is not None:
                 src = os.path.join(sequences, name + ".npz")
                 if not os.path.isfile(src):
@@ -141,11 +157,12 @@ def main(argv=None):
     ap.add_argument("--sequences", default=None)
     ap.add_argument("--stats", default="stats.json")
     ap.add_argument("--resample", action="store_true", help="bring recordings at another rate to the config's on the device")
+    ap.add_argument("--prosody", action="store_true", help="add f0, voiced and energy per frame (audio.PitchEnergy) to each file")
     args = ap.parse_args(argv)
     import yaml
     with open(args.config, "r") as f:
         config = yaml.safe_load(f)
-    run(config, batch=args.batch, sequences=args.sequences, stats_path=args.stats, resample=args.resample)
+    run(config, batch=args.batch, sequences=args.sequences, stats_path=args.stats, resample=args.resample, prosody=args.prosody)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ arithmetic step of the path runs in hand-written HIP kernels behind the C ABI of
 """
 __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionWindow", "dtw_distance", "mel_cepstra",
            "evaluate_synthesis", "MelFrontEnd", "mel_filterbank", "read_wav", "normalize", "denormalize", "Vocoder", "write_wav_pcm16",
-           "Resampler", "resample_table", "read_wav_native"]
+           "Resampler", "resample_table", "read_wav_native", "PitchEnergy", "phoneme_average"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -27,6 +27,9 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
         from . import audio
         return getattr(audio, name)
     if name in ("Resampler", "resample_table", "read_wav_native"):   # band-limited resampler (audio.py)
+        from . import audio
+        return getattr(audio, name)
+    if name in ("PitchEnergy", "phoneme_average"):   # frame pitch and energy, phoneme means (audio.py)
         from . import audio
         return getattr(audio, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

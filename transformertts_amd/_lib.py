@@ -111,6 +111,11 @@ SIGNATURES = {
     "ttts_resample_table_check": (I, [P, Z, I, I, I]),
     "ttts_resample_tile": (I, []),
     "ttts_resample": (I, [P, L, P, I, I, I, I, I, P, P, L, P, P]),
+    "ttts_pitch_lags": (I, []),
+    "ttts_pitch_frames": (I, [I, I, I, I, I]),
+    "ttts_pitch_block": (I, [I, I, I, I, I]),
+    "ttts_pitch_energy": (I, [P, L, P, I, I, I, I, I, I, I, I, I, F, F, P, P, P, P, P, P, P]),
+    "ttts_segment_mean": (I, [P, L, P, P, P, P, L, I, I, I, P, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

@@ -30,6 +30,13 @@ prev; prev = reb; spec = magnitude * t / |t| }, wave = istft(spec).  An utteranc
 
 What `librosa.load(path, sr=...)` does on the way in (csrc/resample.hip): band-limited interpolation, restated from its
 definition (`resample_table`); the output is the front end's input as it is, and the vocoder's output resamples the same way.
+
+    pe = PitchEnergy(config['audio'], device='cuda')           # or front_end=fe: that MelFrontEnd's window table, not a copy
+    out = pe(wave, wave_lens)                                  # {'f0', 'voiced', 'aperiodicity', 'energy': (B, Tmax); 'frames': (B,)}
+    phoneme_average(out['f0'], durations, phoneme_lens, out['frames'], mask=out['voiced'])   # {'mean', 'count'}: (B, Pmax)
+
+Pitch and energy per mel frame and their phoneme means (csrc/pitch.hip): YIN restated from its definition on the front end's
+framing, FastSpeech 2's energy as the L2 norm of the front end's STFT frame, one launch over the ragged batch.
 """
 from __future__ import annotations
 
@@ -652,3 +659,162 @@ class Vocoder:
     def __call__(self, melspec, melspec_lens, init=None, seed: int = 0):
         m = self.magnitude(melspec, melspec_lens)
         return self._griffin_lim(m["spectrogram"], m["melspec_lens"], init, seed)
+
+
+PITCH_MAX_FRAME = 4096                          # pitch.hip PITCH_MAX_F
+
+
+def pitch_lags(sample_rate: float, fmin: float, fmax: float) -> Tuple[int, int]:
+    """-> (tau_min, tau_max) = (floor(sr / fmax), ceil(sr / fmin)): the lags YIN searches"""
+    if not 0.0 < fmin < fmax:
+        raise ValueError(f"PitchEnergy: need 0 < fmin < fmax (fmin {fmin}, fmax {fmax})")
+    return int(math.floor(sample_rate / fmax)), int(math.ceil(sample_rate / fmin))
+
+
+class PitchEnergy:
+    """YIN F0, voicing, aperiodicity and the STFT frame energy of a ragged batch on the device: one launch of csrc/pitch.hip a
+    call, nothing read back, capturable into a HIP graph.
+
+        pe = PitchEnergy(config['audio'], device='cuda')   # or front_end=fe: shares that MelFrontEnd's window table
+        out = pe(wave, wave_lens)                          # {'f0', 'voiced' (bool), 'aperiodicity', 'energy': (B, Tmax); 'frames': (B,)}
+
+    `wave`, `wave_lens` exactly as MelFrontEnd takes them; frame t is mel frame t (centred at t * hop, reflected ends), frames =
+    1 + len // hop, 0 for len <= max(frame_length, n_fft) / 2, rows at or beyond a row's frames are zeros.  d(tau) = sum_{j < window}
+    (x_j - x_{j+tau})^2 as differences squared, d' = d tau / running sum, the first lag in [tau_min, tau_max] under `threshold`
+    followed down its dip, a parabola through its neighbours; unvoiced frames carry f0 = 0 and the minimum of d' as aperiodicity.
+    energy is the L2 norm of the front end's STFT frame (FastSpeech 2's)."""
+
+    def __init__(self, audio_config: Dict, fmin: float = 65.0, fmax: float = 600.0, frame_length: Optional[int] = None,
+                 window: Optional[int] = None, threshold: float = 0.1, device=None, front_end: Optional["MelFrontEnd"] = None):
+        import torch
+        c = audio_config
+        self.sample_rate = int(c["sample_rate"])
+        self.n_fft, self.hop = int(c["n_fft"]), int(c["hop_length"])
+        self.win_length = int(c.get("win_length") or self.n_fft)
+        self.fmin, self.fmax, self.threshold = float(fmin), float(fmax), float(threshold)
+        self.frame_length = self.n_fft if frame_length is None else int(frame_length)
+        self.window = self.frame_length // 2 if window is None else int(window)
+        F, W = self.frame_length, self.window
+        if self.n_fft not in N_FFT:
+            raise ValueError(f"PitchEnergy: n_fft must be one of {N_FFT}, got {self.n_fft}")
+        if not 1 <= self.win_length <= self.n_fft:
+            raise ValueError(f"PitchEnergy: win_length must be in [1, n_fft] (win_length {self.win_length}, n_fft {self.n_fft})")
+        if F < 2 or F % 2 or F > PITCH_MAX_FRAME:
+            raise ValueError(f"PitchEnergy: frame_length must be even and in [2, {PITCH_MAX_FRAME}], got {F}")
+        if not 1 <= self.hop <= F:
+            raise ValueError(f"PitchEnergy: hop_length must be in [1, frame_length] (hop_length {self.hop}, frame_length {F})")
+        if W < 1:
+            raise ValueError(f"PitchEnergy: window must be positive, got {W}")
+        self.tau_min, self.tau_max = pitch_lags(self.sample_rate, self.fmin, self.fmax)
+        if self.tau_min < 2:
+            raise ValueError(f"PitchEnergy: tau_min = floor(sample_rate / fmax) must be at least 2, got {self.tau_min} "
+                             f"(sample_rate {self.sample_rate}, fmax {self.fmax})")
+        if self.tau_min >= self.tau_max:
+            raise ValueError(f"PitchEnergy: tau_min must be below tau_max (tau_min {self.tau_min}, tau_max {self.tau_max})")
+        if W + self.tau_max > F:
+            raise ValueError(f"PitchEnergy: window + tau_max must fit the frame (window {W}, tau_max = ceil(sample_rate / fmin) = "
+                             f"{self.tau_max}, frame_length {F})")
+        if not 0.0 < self.threshold < 1.0:
+            raise ValueError(f"PitchEnergy: threshold must be in (0, 1), got {threshold}")
+        if front_end is not None:
+            if (front_end.n_fft, front_end.win_length, front_end.hop, front_end.sample_rate) != (self.n_fft, self.win_length, self.hop,
+                                                                                               self.sample_rate):
+                raise ValueError("PitchEnergy: front_end was built for another audio config (n_fft, win_length, hop_length, "
+                                 f"sample_rate {front_end.n_fft}, {front_end.win_length}, {front_end.hop}, {front_end.sample_rate})")
+            if device is not None and torch.device(device).type != front_end.device.type:
+                raise ValueError(f"PitchEnergy: front_end lives on {front_end.device}, device is {device}")
+            self.front_end, self.device = front_end, front_end.device
+            self.hann = front_end.tables[HEADER:HEADER + self.n_fft].view(torch.float32)      # the window section, not a copy
+        else:
+            if not torch.cuda.is_available():
+                raise RuntimeError("PitchEnergy needs the HIP device (no CPU fallback)")
+            self.front_end, self.device = None, torch.device(device if device is not None else "cuda")
+            self.hann = torch.from_numpy(hann_window(self.win_length, self.n_fft).astype(np.float32)).to(self.device)
+
+    def _chk(self, t, name, dtype):
+        if not t.is_cuda:
+            raise ValueError(f"PitchEnergy.{name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback), got {t.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"PitchEnergy.{name}: expected dtype {dtype}, got {t.dtype}")
+
+    def _lens(self, lens, B, name):
+        import torch
+        if tuple(lens.shape) != (B,):
+            raise ValueError(f"PitchEnergy.{name} must have shape ({B},), got {tuple(lens.shape)}")
+        if lens.dtype.is_floating_point or lens.dtype == torch.bool:
+            raise ValueError(f"PitchEnergy.{name} must be integers, got {lens.dtype}")
+        if not lens.is_cuda:                       # host lengths: the one place the unreflectable length can be refused
+            half = max(self.frame_length, self.n_fft) // 2
+            if lens.numel() and int(lens.min()) <= half:
+                raise ValueError(f"PitchEnergy.{name}: an utterance of {int(lens.min())} samples cannot be reflected "
+                                 f"(max(frame_length, n_fft)/2 + 1 = {half + 1} at the least)")
+            lens = lens.to(self.device)
+        return lens.to(torch.int64).contiguous()
+
+    def __call__(self, wave, wave_lens):
+        import torch
+        from . import _lib
+        from .ops import _p, _stream
+        if wave.dim() != 2 or min(wave.shape) < 1:
+            raise ValueError(f"PitchEnergy: wave must be (B, Nmax), got {tuple(wave.shape)}")
+        self._chk(wave, "wave", torch.float32)
+        B, Nmax = wave.shape
+        lens = self._lens(wave_lens, B, "wave_lens")
+        wave = wave.detach()
+        if (Nmax > 1 and wave.stride(1) != 1) or (B > 1 and wave.stride(0) < Nmax):
+            wave = wave.contiguous()
+        ld = wave.stride(0) if B > 1 else Nmax
+        Tmax = 1 + Nmax // self.hop
+        f0, aper, energy = (torch.empty(B, Tmax, dtype=torch.float32, device=wave.device) for _ in range(3))
+        voiced = torch.empty(B, Tmax, dtype=torch.uint8, device=wave.device)
+        frames = torch.empty(B, dtype=torch.int64, device=wave.device)
+        _lib.check(_lib.load().ttts_pitch_energy(_p(wave), ld, _p(lens), B, Nmax, self.n_fft, self.win_length, self.hop, self.frame_length,
+                                                 self.window, self.tau_min, self.tau_max, float(self.sample_rate), self.threshold,
+                                                 _p(self.hann), _p(f0), _p(voiced), _p(aper), _p(energy), _p(frames), _stream()),
+                   "ttts_pitch_energy")
+        return {"f0": f0, "voiced": voiced.view(torch.bool), "aperiodicity": aper, "energy": energy, "frames": frames}
+
+
+def phoneme_average(values, durations, phoneme_lens, frames, mask=None):
+    """frame values -> phoneme means (csrc/pitch.hip ttts_segment_mean, one launch, nothing read back).  values (B, Tmax) fp32,
+    durations (B, Pmax) int64 as `extract_durations` returns them, phoneme_lens and frames (B,) integers, mask (B, Tmax) bool or
+    uint8 or None -> {'mean': (B, Pmax) fp32, 'count': (B, Pmax) int32}.  Phoneme p covers frames [c_p, c_p + dur_p), c the
+    exclusive prefix sum, clipped to frames[b]; the mean is over the frames the mask keeps, 0 when there is none.
+    phoneme_average(f0, ..., mask=voiced) is FastSpeech 2's phoneme pitch, phoneme_average(energy, ...) its phoneme energy."""
+    import torch
+    from . import _lib
+    from .ops import _p, _stream
+    if values.dim() != 2 or min(values.shape) < 1:
+        raise ValueError(f"phoneme_average: values must be (B, Tmax), got {tuple(values.shape)}")
+    if not values.is_cuda:
+        raise ValueError(f"phoneme_average.values: expected a CUDA/HIP tensor (the HIP path has no CPU fallback), got {values.device}")
+    if values.dtype != torch.float32:
+        raise ValueError(f"phoneme_average.values: expected dtype {torch.float32}, got {values.dtype}")
+    B, Tmax = values.shape
+    if durations.dim() != 2 or durations.size(0) != B or durations.size(1) < 1:
+        raise ValueError(f"phoneme_average: durations must be ({B}, Pmax), got {tuple(durations.shape)}")
+    if durations.dtype != torch.int64:
+        raise ValueError(f"phoneme_average.durations: expected dtype {torch.int64}, got {durations.dtype}")
+    Pmax = durations.size(1)
+    for t, name in ((phoneme_lens, "phoneme_lens"), (frames, "frames")):
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"phoneme_average.{name} must have shape ({B},), got {tuple(t.shape)}")
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"phoneme_average.{name} must be integers, got {t.dtype}")
+    if mask is not None:
+        if tuple(mask.shape) != (B, Tmax):
+            raise ValueError(f"phoneme_average: mask must be ({B}, {Tmax}) like values, got {tuple(mask.shape)}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"phoneme_average.mask: expected dtype {torch.bool} or {torch.uint8}, got {mask.dtype}")
+        mask = mask.to(values.device).contiguous().view(torch.uint8)
+    lens = [t.to(values.device).to(torch.int64).contiguous() for t in (phoneme_lens, frames)]
+    values = values.detach()
+    if (Tmax > 1 and values.stride(1) != 1) or (B > 1 and values.stride(0) < Tmax):
+        values = values.contiguous()
+    ld = values.stride(0) if B > 1 else Tmax
+    dur = durations.to(values.device).contiguous()
+    mean = torch.empty(B, Pmax, dtype=torch.float32, device=values.device)
+    count = torch.empty(B, Pmax, dtype=torch.int32, device=values.device)
+    _lib.check(_lib.load().ttts_segment_mean(_p(values), ld, _p(dur), _p(lens[0]), _p(lens[1]), _p(mask), Tmax, B, Tmax, Pmax, _p(mean),
+                                             _p(count), _stream()), "ttts_segment_mean")
+    return {"mean": mean, "count": count}
