@@ -744,6 +744,57 @@ int ttts_pitch_energy(const float* wave, int64_t ld_batch, const int64_t* wave_l
 int ttts_segment_mean(const float* values, int64_t ld_values, const int64_t* durations, const int64_t* phoneme_lens,
                       const int64_t* frames, const uint8_t* mask, int64_t ld_mask, int B, int Tmax, int Pmax, float* mean,
                       int32_t* counts, void* stream);
+/* ---- Variance adaptor of a FastSpeech-2-style student: length regulator and its transpose, durations from predicted
+ * log-durations, quantised pitch / energy embeddings, three masked regression losses (variance.hip; additive, the ABI version
+ * stays 24).  Throughout pl_b = phoneme_lens[b] clamped to [0, Pmax]; dur'_p = max(durations[b, p], 0) for p < pl_b, else 0;
+ * c the exclusive prefix sum of dur'; frames_b = min(sum dur', Tmax).
+ *   regulator   ttts_length_regulate_fwd: y[b, t, :] = x[b, p(t), :] for t < frames_b, where c_p <= t < c_p + dur'_p; exact zeros
+ *               from frames_b on.  x is (B, Pmax, D) fp32 at row stride ld_row and batch stride ld_batch (floats), y (B, Tmax, D)
+ *               packed; mel_lens[b] = frames_b (int64); index[b, t] = p(t), -1 from frames_b on (int32).  One launch, a
+ *               workgroup per ttts_length_regulate_frames frames of an utterance.
+ *   transpose   ttts_length_regulate_bwd: dx[b, p, :] = the fp32 sum of dy[b, t, :] over t in [c_p, min(c_p + dur'_p, frames_b))
+ *               in ascending t, one plain add per frame from 0.f -- bit for bit a sequential fp32 loop; exact zeros for a phoneme
+ *               without a frame and for p >= pl_b.  dy (B, Tmax, D) and dx (B, Pmax, D) packed; accumulate != 0: dx += that sum.
+ *   durations   ttts_durations_from_log: d = rint((exp(log_d) - 1) alpha) evaluated in fp64 from the fp32 input, halves to even,
+ *               clamped to [0, 2^31 - 1]; 0 for a NaN or infinite log_d; then max(d, min_duration) for p < pl_b; 0 for p >= pl_b.
+ *   embedding   ttts_variance_embed_fwd: i = the number of pitch_bins (n_pitch - 1 ascending fp32 boundaries) strictly below
+ *               pitch[b, p] -- torch.bucketize with right=False; a NaN value gives 0 -- and j alike for the energy; y = (x +
+ *               pitch_table[i]) + energy_table[j] in that order for p < pl_b, y = x behind it; pitch_ids / energy_ids (B, Pmax)
+ *               int64 hold i / j, -1 behind it.  A NULL table skips that feature: its other pointers are not touched.  The
+ *               backward needs no kernel of its own: dx = dy, and the table gradients are ttts_embedding_bwd on the saved ids (it
+ *               compares ids for equality with a table row, so -1 contributes nowhere and is never an index).
+ *   loss        ttts_variance_loss_fwd: out[0 .. 2] = the means over the n = sum_b pl_b valid phonemes of (log_d_pred -
+ *               fp32(log_fp64(dur' + 1)))^2, (pitch_pred - pitch_target)^2, (energy_pred - energy_target)^2, all (B, Pmax) packed;
+ *               out[3] = (w_d out[0] + w_p out[1]) + w_e out[2]; exactly 0 when n = 0.  One workgroup of 1024 threads: thread i
+ *               adds the squares of the flat elements i, i + 1024, ... in ascending order (plain multiply, plain add, from 0.f,
+ *               elements behind a length skipped); the 64 lanes of a wave meet in a butterfly (lane l adds lane l ^ 32, then
+ *               l ^ 16, ... l ^ 1); the 16 wave sums are added in ascending order from 0.f; then one division by (float)n.
+ *               ttts_variance_loss_bwd: with gout the gradient of the four outputs, s_k = (2 / (float)n) * (gout[k] + w_k *
+ *               gout[3]) and d_pred_k = s_k * (pred_k - target_k) for p < pl_b, exact 0 behind it and everywhere when n = 0;
+ *               every product, sum and quotient rounded on its own.  One launch writes the three gradients.
+ * No host read, no allocation, no atomics, the same bits whatever the grid, the batch or the call, capturable into a HIP graph;
+ * nothing at or behind a length is read (the embedding passes x rows through).  Refused before any launch, with a message that
+ * names the value: null pointers, B outside [1, 65535], Pmax outside [1, 4096], Tmax outside [1, 2^20], D outside [4, 4096] or
+ * no multiple of 4, n_pitch / n_energy outside [2, 4096], strides that do not cover a row or are no multiple of 4, alpha not
+ * positive and finite, min_duration < 0, weights not finite, misaligned pointers (16 bytes for the float rows, 8 for int64, 4
+ * for the other arrays). */
+int ttts_length_regulate_frames(void);
+int ttts_length_regulate_fwd(const float* x, int64_t ld_row, int64_t ld_batch, const int64_t* durations, const int64_t* phoneme_lens,
+                             int B, int Pmax, int Tmax, int D, float* y, int64_t* mel_lens, int32_t* index, void* stream);
+int ttts_length_regulate_bwd(const float* dy, const int64_t* durations, const int64_t* phoneme_lens, int B, int Pmax, int Tmax, int D,
+                             float* dx, int accumulate, void* stream);
+int ttts_durations_from_log(const float* log_d, const int64_t* phoneme_lens, int B, int Pmax, float alpha, int64_t min_duration,
+                            int64_t* durations, void* stream);
+int ttts_variance_embed_fwd(const float* x, int64_t ld_row, int64_t ld_batch, const float* pitch, const float* energy,
+                            const float* pitch_bins, int n_pitch, const float* energy_bins, int n_energy, const float* pitch_table,
+                            const float* energy_table, const int64_t* phoneme_lens, int B, int Pmax, int D, float* y,
+                            int64_t* pitch_ids, int64_t* energy_ids, void* stream);
+int ttts_variance_loss_fwd(const float* log_d_pred, const int64_t* durations, const float* pitch_pred, const float* pitch_target,
+                           const float* energy_pred, const float* energy_target, const int64_t* phoneme_lens, int B, int Pmax, float w_d,
+                           float w_p, float w_e, float* out, void* stream);
+int ttts_variance_loss_bwd(const float* log_d_pred, const int64_t* durations, const float* pitch_pred, const float* pitch_target,
+                           const float* energy_pred, const float* energy_target, const int64_t* phoneme_lens, int B, int Pmax, float w_d,
+                           float w_p, float w_e, const float* gout, float* d_log_d, float* d_pitch, float* d_energy, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

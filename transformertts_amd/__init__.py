@@ -7,7 +7,9 @@ arithmetic step of the path runs in hand-written HIP kernels behind the C ABI of
 """
 __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionWindow", "dtw_distance", "mel_cepstra",
            "evaluate_synthesis", "MelFrontEnd", "mel_filterbank", "read_wav", "normalize", "denormalize", "Vocoder", "write_wav_pcm16",
-           "Resampler", "resample_table", "read_wav_native", "PitchEnergy", "phoneme_average"]
+           "Resampler", "resample_table", "read_wav_native", "PitchEnergy", "phoneme_average", "length_regulate", "LengthRegulator",
+           "durations_from_log", "variance_embed", "VarianceEmbedding", "variance_bins", "VarianceLoss", "VariancePredictor",
+           "VarianceAdaptor"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -32,4 +34,8 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
     if name in ("PitchEnergy", "phoneme_average"):   # frame pitch and energy, phoneme means (audio.py)
         from . import audio
         return getattr(audio, name)
+    if name in ("length_regulate", "LengthRegulator", "durations_from_log", "variance_embed", "VarianceEmbedding", "variance_bins",
+                "VarianceLoss", "VariancePredictor", "VarianceAdaptor"):   # variance adaptor of a FastSpeech-2 student (variance.py)
+        from . import variance
+        return getattr(variance, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -116,6 +116,13 @@ SIGNATURES = {
     "ttts_pitch_block": (I, [I, I, I, I, I]),
     "ttts_pitch_energy": (I, [P, L, P, I, I, I, I, I, I, I, I, I, F, F, P, P, P, P, P, P, P]),
     "ttts_segment_mean": (I, [P, L, P, P, P, P, L, I, I, I, P, P, P]),
+    "ttts_length_regulate_frames": (I, []),
+    "ttts_length_regulate_fwd": (I, [P, L, L, P, P, I, I, I, I, P, P, P, P]),
+    "ttts_length_regulate_bwd": (I, [P, P, P, I, I, I, I, P, I, P]),
+    "ttts_durations_from_log": (I, [P, P, I, I, F, L, P, P]),
+    "ttts_variance_embed_fwd": (I, [P, L, L, P, P, P, I, P, I, P, P, P, I, I, I, P, P, P, P]),
+    "ttts_variance_loss_fwd": (I, [P, P, P, P, P, P, P, I, I, F, F, F, P, P]),
+    "ttts_variance_loss_bwd": (I, [P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),
