@@ -285,7 +285,8 @@ int ttts_conv1d_bwd_weight_h3(const float* dy, const float* x, float* dw, float*
  * n writes 1/n of the partial sums of a launch of its own.  ttts_wgrad_group_ok: the CLASS of a problem -- 0: no member of any group; 1: the
  * 4-wave 128 x 128 tile; 2: whole 256 x 256 tiles on the 8-wave LDS-DMA kernel (the FFN, packed in-projection and post-net
  * convolution weights over long row ranges); 3 / 4: the 128 x 96 / 96 x 128 tiles of weights with 80 input / output channels
- * (the mel side) -- the members of one launch share a class.  (The autograd of torch.nn.Linear /
+ * (the mel side) -- the members of one launch share a class.  A convolution member's tap count must be odd, as in the single
+ * entries: the launch refuses an even one ("taps=<n>"), although the class query answers for it.  (The autograd of torch.nn.Linear /
  * nn.Conv1d runs these one by one: model/module.py:4-53 and the torch layers of model/model.py:189-213.) */
 int ttts_wgrad_group_ok(int64_t M, int N, int K, int taps);
 int ttts_wgrad_group(int n, const float* const* dy, const float* const* x, float* const* dw, float* const* dbias,

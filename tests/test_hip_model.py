@@ -80,6 +80,8 @@ def _oracle64(cfg, w_seed):
                                                             ("base", 16, 100, 870, 15, 25),
                                                             ("micro", 3, 12, 40, 16, 26),       # d_model 32, head_dim 16
                                                             ("tiny1h", 3, 12, 40, 18, 28),      # d_model 128, ONE head of 128 columns
+                                                            # `tiny` with 3-tap pre-net and 7-tap post-net convolutions
+                                                            ("tiny_k37", 3, 12, 40, 19, 29),
                                                             # utterances far beyond LJSpeech's longest (870 frames): 24
                                                             # query blocks, 47 key tiles, 3000 rows of the 5000-row pe table
                                                             ("base", 2, 200, 3000, 17, 27)])
@@ -530,9 +532,18 @@ def test_twin_keywords_refuse_misuse():
     assert out2["post_melspec"] is not None and torch.isfinite(out2["post_melspec"]).all() and out2["pred_stop"] is not None
 
 
-@pytest.mark.parametrize("flag,B,Tp,Tm", [("TWIN_ENCODER", 4, 64, 200), ("TWIN_ENCODER", 3, 37, 150), ("TWIN_POSTNET", 4, 64, 200),
-                                          ("TWIN_POSTNET", 3, 37, 150), ("TWIN_POSTNET", 32, 50, 870)])
-def test_twin_batches_are_the_two_forwards(flag, B, Tp, Tm):
+def _twin_row(flag, B, Tp, Tm, cfg_name="base"):
+    """(the rows of the base configuration keep the ids they had before the configuration was a parameter)"""
+    return pytest.param(flag, B, Tp, Tm, cfg_name, id=f"{flag}-{B}-{Tp}-{Tm}" + ("" if cfg_name == "base" else f"-{cfg_name}"))
+
+
+@pytest.mark.parametrize("flag,B,Tp,Tm,cfg_name", [_twin_row("TWIN_ENCODER", 4, 64, 200), _twin_row("TWIN_ENCODER", 3, 37, 150),
+                                                   _twin_row("TWIN_POSTNET", 4, 64, 200), _twin_row("TWIN_POSTNET", 3, 37, 150),
+                                                   _twin_row("TWIN_POSTNET", 32, 50, 870),
+                                                   # 3-tap pre-net / 7-tap post-net convolutions under the twin batch
+                                                   _twin_row("TWIN_ENCODER", 3, 37, 150, "tiny_k37"),
+                                                   _twin_row("TWIN_POSTNET", 3, 37, 150, "tiny_k37")])
+def test_twin_batches_are_the_two_forwards(flag, B, Tp, Tm, cfg_name):
     """model.encode_twin: the encoder of BOTH forwards of training_step as one pass over a batch of 2 B (the reference encodes the
     same phonemes twice, lightning_module.py:53-59,77).  With dropout off the step must be the step of two separate encodes:
     loss, every parameter gradient, the pre-net's BatchNorm running statistics (updated TWICE, by each forward's own batch
@@ -546,7 +557,7 @@ def test_twin_batches_are_the_two_forwards(flag, B, Tp, Tm):
     from oracle import model_config, fill_state, synth_batch
     from transformertts_amd import ops
     from transformertts_amd.lightning_module import LightningModule
-    cfg = model_config("base")
+    cfg = model_config(cfg_name)
     config = {"model": dict(cfg, device="cuda"), "loss": {"stop_weight": 8.0},
               "training": {"num_epochs": 300, "teacher_forcing_mode": "linear", "warmup_steps": 4000}}
     batch = synth_batch(B, Tp, Tm, cfg["n_mels"], cfg["n_phon"], ragged=True, seed=31)

@@ -542,6 +542,10 @@ def test_fp16x3_conv_forward_agrees_with_fp64(B, T, cin, cout):
                                                  (48, 870, 256, 256, 3.0),      # 41 760 rows: the 224-row one-wave-per-SIMD tile with the
                                                  (61, 401, 256, 256, 0.0)])     # clipping loader + this epilogue (ragged last tile too)
 def test_batchnorm_statistics_from_the_conv_epilogue(B, T, cin, cout, offset):
+    _bn_statistics_from_the_conv_epilogue(B, T, cin, cout, offset, 5)
+
+
+def _bn_statistics_from_the_conv_epilogue(B, T, cin, cout, offset, taps, report=None):
     """The fp16x3 convolution leaves BatchNorm's row-chunk partials (count, mean, M2 per channel) behind in its epilogue and
     ttts_bn_train_stats_from_partials merges them: same mean / invstd / running statistics as the separate two-pass
     statistics kernel and as fp64, also for ragged row counts (rows past M do not count) and for a channel offset 40 x
@@ -550,14 +554,14 @@ def test_batchnorm_statistics_from_the_conv_epilogue(B, T, cin, cout, offset):
     from transformertts_amd.ops import _p, _stream
     lib = _lib.load()
     M = B * T
-    x, w = _rand(B, T, cin, seed=1), _rand(cout, cin, 5, seed=2, scale=(5 * cin) ** -0.5)
+    x, w = _rand(B, T, cin, seed=1), _rand(cout, cin, taps, seed=2, scale=(taps * cin) ** -0.5)
     b = _rand(cout, seed=3) + offset
-    nblk = lib.ttts_conv1d_fwd_h3_bn_blocks(B, T, cin, cout, 5)
+    nblk = lib.ttts_conv1d_fwd_h3_bn_blocks(B, T, cin, cout, taps)
     assert 0 < nblk <= 512
     y = torch.empty(B, T, cout, device=_dev())
     ws = ops._ws(lib.ttts_bn_workspace_bytes(M, cout), _dev())
-    pl = ops._planes(w, 6, cout, 5 * cin, cin, 5)
-    assert lib.ttts_conv1d_fwd_h3(_p(x), _p(pl), _p(b), _p(y), B, T, cin, cout, 5, _p(ops._amax(x)), _p(ws), _stream()) == 0
+    pl = ops._planes(w, 6, cout, taps * cin, cin, taps)
+    assert lib.ttts_conv1d_fwd_h3(_p(x), _p(pl), _p(b), _p(y), B, T, cin, cout, taps, _p(ops._amax(x)), _p(ws), _stream()) == 0
     res = []
     for fused in (True, False):
         mean, invstd = torch.empty(cout, device=_dev()), torch.empty(cout, device=_dev())
@@ -573,15 +577,18 @@ def test_batchnorm_statistics_from_the_conv_epilogue(B, T, cin, cout, offset):
     yd = y.double().view(M, cout)
     mean64, var64 = yd.mean(0), yd.var(0, unbiased=False)
     inv64 = 1.0 / torch.sqrt(var64 + 1e-5)
-    for mean, invstd, rm, rv, n in res:
+    for how, (mean, invstd, rm, rv, n) in zip(("from partials", "two-pass"), res):
         assert n == 1
+        if report is not None:
+            report(f"{how}: mean abs {float((mean.double() - mean64).abs().max()):.3e} invstd {_rel(invstd, inv64):.3e} "
+                   f"running_var {_rel(rv, 0.9 + 0.1 * yd.var(0, unbiased=True)):.3e}")
         assert float((mean.double() - mean64).abs().max()) < 2e-6 * (1.0 + abs(offset)) and _rel(invstd, inv64) < 2e-6, \
             (float((mean.double() - mean64).abs().max()), _rel(invstd, inv64))
         assert _rel(rv, 0.9 + 0.1 * yd.var(0, unbiased=True)) < 2e-6
     assert _rel(res[0][1], res[1][1]) < 1e-6 and _rel(res[0][0], res[1][0]) < 1e-6
     # the plain forward (no partials) writes the same y
     y2 = torch.empty_like(y)
-    assert lib.ttts_conv1d_fwd_h3(_p(x), _p(pl), _p(b), _p(y2), B, T, cin, cout, 5, _p(ops._amax(x)), None, _stream()) == 0
+    assert lib.ttts_conv1d_fwd_h3(_p(x), _p(pl), _p(b), _p(y2), B, T, cin, cout, taps, _p(ops._amax(x)), None, _stream()) == 0
     assert torch.equal(y, y2)
 
 
@@ -589,6 +596,10 @@ def test_batchnorm_statistics_from_the_conv_epilogue(B, T, cin, cout, offset):
                                                  (64, 870, 256, 256, 3.0),      # the 224-row tile: 55 680 = 248 chunks + 128 rows
                                                  (32, 870, 256, 256, 0.0)])     # 27 840 rows: 64-row chunks, the last tile's last chunk empty
 def test_batchnorm_statistics_of_each_half_of_a_twin_batch(B, T, cin, cout, offset):
+    _bn_statistics_of_each_half_of_a_twin_batch(B, T, cin, cout, offset, 5)
+
+
+def _bn_statistics_of_each_half_of_a_twin_batch(B, T, cin, cout, offset, taps, report=None):
     """ttts_bn_train_stats_from_partials_rows: the statistics of EACH HALF of the rows of one convolution (a twin batch)
     from the epilogue's row-chunk partials -- a half's whole chunks -- plus the rows of the chunk the halves share, read from y
     itself: mean / invstd / running statistics of each half against fp64 over its own rows, the no-grad half (the second) first."""
@@ -596,16 +607,16 @@ def test_batchnorm_statistics_of_each_half_of_a_twin_batch(B, T, cin, cout, offs
     from transformertts_amd.ops import _p, _off, _stream
     lib = _lib.load()
     M2, M = B * T, B * T // 2
-    x, w = _rand(B, T, cin, seed=1), _rand(cout, cin, 5, seed=2, scale=(5 * cin) ** -0.5)
+    x, w = _rand(B, T, cin, seed=1), _rand(cout, cin, taps, seed=2, scale=(taps * cin) ** -0.5)
     x[B // 2:] *= 1.7                                               # (the halves differ)
     b = _rand(cout, seed=3) + offset
-    nblk = lib.ttts_conv1d_fwd_h3_bn_blocks(B, T, cin, cout, 5)
-    chunk = lib.ttts_conv1d_fwd_h3_bn_chunk_rows(B, T, cin, cout, 5)
+    nblk = lib.ttts_conv1d_fwd_h3_bn_blocks(B, T, cin, cout, taps)
+    chunk = lib.ttts_conv1d_fwd_h3_bn_chunk_rows(B, T, cin, cout, taps)
     assert 0 < nblk <= 512 and 0 < chunk <= 256 and nblk >= -(-M2 // chunk)
     y = torch.empty(B, T, cout, device=_dev())
     ws = ops._ws(lib.ttts_bn_workspace_bytes(M2, cout), _dev())
-    pl = ops._planes(w, 6, cout, 5 * cin, cin, 5)
-    assert lib.ttts_conv1d_fwd_h3(_p(x), _p(pl), _p(b), _p(y), B, T, cin, cout, 5, _p(ops._amax(x)), _p(ws), _stream()) == 0
+    pl = ops._planes(w, 6, cout, taps * cin, cin, taps)
+    assert lib.ttts_conv1d_fwd_h3(_p(x), _p(pl), _p(b), _p(y), B, T, cin, cout, taps, _p(ops._amax(x)), _p(ws), _stream()) == 0
     s_, cut = divmod(M, chunk)
     runs = {0: (0, s_, s_ * chunk, cut), 1: (s_ + 1, nblk - s_ - 1, M, min((s_ + 1) * chunk, M2) - M)} if cut else \
            {0: (0, s_, 0, 0), 1: (s_, nblk - s_, 0, 0)}
@@ -621,6 +632,9 @@ def test_batchnorm_statistics_of_each_half_of_a_twin_batch(B, T, cin, cout, offs
         mean64, var64 = half.mean(0), half.var(0, unbiased=False)
         rm64 = 0.9 * rm64 + 0.1 * mean64
         rv64 = 0.9 * rv64 + 0.1 * half.var(0, unbiased=True)
+        if report is not None:
+            report(f"half {h}: mean abs {float((mean.double() - mean64).abs().max()):.3e} "
+                   f"invstd {_rel(invstd, 1.0 / torch.sqrt(var64 + 1e-5)):.3e}")
         assert float((mean.double() - mean64).abs().max()) < 2e-6 * (1.0 + abs(offset)), (h, float((mean.double() - mean64).abs().max()))
         assert _rel(invstd, 1.0 / torch.sqrt(var64 + 1e-5)) < 2e-6, (h, _rel(invstd, 1.0 / torch.sqrt(var64 + 1e-5)))
     assert int(nbt) == 2 and _rel(rv, rv64) < 2e-6 and float((rm.double() - rm64).abs().max()) < 2e-6 * (1.0 + abs(offset))

@@ -98,8 +98,12 @@ def test_linear_forward_on_the_bf16x6_shape_fallback(M, N, K, act, res):
                                                         (2, 64, 256, 256, 2, False), (5, 1, 16, 128, 2, True),
                                                         (31, 870, 256, 256, 2, True), (61, 433, 80, 256, 0, True)])
 def test_conv_bn_fwd_bwd(B, T, cin, cout, act, training):
+    _conv_bn_fwd_bwd(B, T, cin, cout, act, training, 5)
+
+
+def _conv_bn_fwd_bwd(B, T, cin, cout, act, training, k, report=None):
+    """z = act(BatchNorm1d(Conv1d_same(x))) with k taps and its backward chain through ops.conv_bn against fp64 on the CPU"""
     from transformertts_amd import ops
-    k = 5
     x = _rand(B, T, cin, seed=1)
     w = _rand(cout, cin, k, seed=2, scale=(cin * k) ** -0.5)
     b = _rand(cout, seed=3, scale=0.1)
@@ -109,7 +113,7 @@ def test_conv_bn_fwd_bwd(B, T, cin, cout, act, training):
     dz = _rand(B, T, cout, seed=8)
     xd, wd, bd, gd, bed = [t.double().requires_grad_() for t in (x, w, b, gamma, beta)]
     rmd, rvd = rm.double().clone(), rv.double().clone()
-    y = F.conv1d(xd.transpose(1, 2), wd, bd, padding=2)
+    y = F.conv1d(xd.transpose(1, 2), wd, bd, padding=k // 2)
     y = F.batch_norm(y, rmd, rvd, gd, bed, training=training, momentum=0.1, eps=1e-5).transpose(1, 2)
     ref = torch.tanh(y) if act == 2 else y
     if training:
@@ -118,9 +122,15 @@ def test_conv_bn_fwd_bwd(B, T, cin, cout, act, training):
     rmg, rvg = rm.to(_dev()), rv.to(_dev())
     nbt = torch.zeros((), dtype=torch.int64, device=_dev())
     z = ops.conv_bn(xg, wg, bg, gg, beg, rmg, rvg, nbt, training, 0.1, 1e-5, act, 0.0, 0)
+    if report is not None:
+        report(f"z {rel_l2(z, ref):.3e}")
     assert rel_l2(z, ref) < TOL
     if training:
         z.backward(dz.to(_dev()))
+        if report is not None:
+            report(f"running_mean {rel_l2(rmg, rmd):.3e} running_var {rel_l2(rvg, rvd):.3e} dx {rel_l2(xg.grad, xd.grad):.3e} "
+                   f"dw {rel_l2(wg.grad, wd.grad):.3e} dgamma {rel_l2(gg.grad, gd.grad):.3e} dbeta {rel_l2(beg.grad, bed.grad):.3e} "
+                   f"max|dbias| {bg.grad.abs().max().item():.3e} (bound {1e-3 * dz.abs().sum().item() / cout:.3e})")
         assert int(nbt.item()) == 1
         assert rel_l2(rmg, rmd) < TOL and rel_l2(rvg, rvd) < TOL
         assert rel_l2(xg.grad, xd.grad) < TOL

@@ -122,6 +122,8 @@ def _rows(name):
         row("shift_ragged_T", "needs its utterance length", row_shift=[1], T=[7])
         row("conv_without_T", "needs its utterance length", taps=[5], T=[0])
         row("conv_with_shift", "takes no row shift", taps=[5], T=[320], row_shift=[1])
+        # ttts_wgrad_group_ok(640, 256, 256, 4) answers class 1, as for any tap count: the parity is the launch's own check
+        row("even_taps", "taps=4", "accepted", taps=[4], T=[320])
         # class 2 (whole 256 x 256 tiles by LDS-DMA) clips utterances of at least 16 rows only
         row("class2_short_T", "needs its utterance length", M=[25632], N=[1024], K=[256], row_shift=[1], T=[8])
     return rows
@@ -434,3 +436,17 @@ def test_a_group_reaches_the_library_in_abi_order(monkeypatch):
     queue.launch_wgrads()
     assert [(e, a[0], list(a[7]), list(a[1])) for e, a in lib.calls] == [("wgrad_group", 1, [6400], [f[6].addr])]
     assert not any(queue.wg.values())
+
+
+@pytest.mark.parametrize("with_queue", [0, 1])
+def test_an_even_tap_count_reaches_neither_a_group_nor_an_entry(monkeypatch, with_queue):
+    """`ops._weight_grad` / `ReduceQueue.defer_wgrad` refuse a convolution with an even tap count themselves: the class query
+    answers 1 for (640, 256, 256, 4), so without the guard the member would wait in a group."""
+    ops, lib, queue = _install(monkeypatch, True, True)
+    assert lib.real.ttts_wgrad_group_ok(640, 256, 256, 4) == 1
+    f = [_Fake(f"t{i}") for i in range(6)]
+    with pytest.raises(ValueError, match="taps=4"):
+        ops._weight_grad(*f, 1, queue if with_queue else None, 640, 256, 256, 4, 320, 0, True)
+    with pytest.raises(ValueError, match="taps=4"):
+        queue.defer_wgrad(1, *f, 640, 256, 256, 4, 320)
+    assert lib.calls == [] and not any(queue.wg.values())

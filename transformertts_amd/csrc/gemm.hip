@@ -1239,6 +1239,9 @@ int ttts_wgrad_group(int n, const float* const* dy, const float* const* x, float
         pb[i] = {dy[i], x[i], ws[i], ws_bytes[i], M[i], N[i], K[i], taps[i], 0, T[i], row_shift[i], dy_amax[i], x_amax[i], taps[i] > 1,
                  dbias != nullptr && dbias[i] != nullptr};
         ENTRY_REQUIRE(dy[i] && x[i] && dw[i] && ws[i] && dy_amax[i] && x_amax[i], "null pointer (member %d)", i);
+        // (the class query answers for any tap count; "same" padding is symmetric for odd ones only, as in the single entries)
+        ENTRY_REQUIRE(taps[i] <= 1 || (taps[i] & 1), "member %d: bad dims M=%lld N=%d K=%d taps=%d (a convolution's tap count must be odd)", i,
+                      (long long)M[i], N[i], K[i], taps[i]);
         long tiles = 0;
         ENTRY_REQUIRE(grp.cls != 0 && wgrad_class(M[i], N[i], K[i], taps[i], &tiles) == grp.cls && M[i] < (1LL << 31),
                       "member %d (M=%lld N=%d K=%d taps=%d) is not of the group's class %d", i, (long long)M[i], N[i], K[i], taps[i], grp.cls);

@@ -449,6 +449,8 @@ class ReduceQueue:
         """dw (+)= dy^T x, db (+)= column sums of dy (taps > 1: a convolution's weight gradient over utterances of T rows) --
         later, in a grouped launch of class `cls` (backward nodes only).  Members of one group share a row count: their
         workgroups then walk equally long row ranges."""
+        if taps > 1 and taps % 2 == 0:
+            raise ValueError(f"defer_wgrad: a convolution's tap count must be odd (taps={taps})")
         self._arm()
         pend = self.wg[cls]
         if pend and (pend[0].M != M or pend[0].dy.device != dy.device):
@@ -564,6 +566,9 @@ def _weight_grad(dy, dy_amax, x, x_amax, dw, db, acc: int, queue, M: int, N: int
     a gradient sink with a queue (nobody reads it before the optimizer: `ReduceQueue.defer_wgrad`), launched now otherwise.
     A Linear's (M rows, N x K weight; `row_shift` / T: the shifted loader) or, `conv`, a convolution's over utterances of T
     rows (N = cout, K = cin)."""
+    if conv and taps % 2 == 0:
+        # (ttts_wgrad_group_ok answers a class for any tap count; "same" padding is symmetric for odd ones only)
+        raise ValueError(f"_weight_grad: a convolution's tap count must be odd (taps={taps})")
     lib = _lib.load()
     cls = lib.ttts_wgrad_group_ok(M, N, K, taps) if (WGRAD_GROUPS and DEFER_REDUCE and queue is not None and
                                                      _wgrad_is_split(N, K)) else 0
