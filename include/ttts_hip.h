@@ -1013,6 +1013,33 @@ int ttts_decode_attention_window(const float* q, int64_t ldq, const float* k, co
  * zero by itself).  16-byte stores when C % 4 == 0 and x is 16-byte aligned.  outer <= 65535. */
 int ttts_mask_rows(float* x, const int64_t* lens, int64_t outer, int group, int64_t T, int64_t C, void* stream);
 
+/* ---- additive (ABI 24): a length-masked Conv1d -> ReLU -> LayerNorm -> Dropout stage (predictor.hip) ------------------------
+ * The building block of FastSpeech 2's variance predictors and FFT blocks, on (B, Pmax, C) fp32 rows of ragged utterances.
+ * x is addressed through (ld_row, ld_batch) as the variance entries address it; pl_b = clamp(lens[b], 0, Pmax); w (Cout, Cin, taps)
+ * and bias as nn.Conv1d holds them, gamma / beta as nn.LayerNorm.
+ *   x'[b, p] = x[b, p] for p < pl_b, exact zeros elsewhere (memory at or behind a length is never read)
+ *   z = bias + sum_j sum_ci w[co, ci, j] x'[b, p + j - taps / 2, ci];  r = max(z, 0);  mean, rstd = 1 / sqrt(var + eps) over co (biased)
+ *   y = ((r - mean) rstd) gamma + beta, times keep_elem(seed ^ *step_seed, flat index in (B, Pmax, Cout)) / (1 - drop_p) when drop_p > 0
+ * y (B, Pmax, Cout) is fully written: exact zeros for p >= pl_b.  r (B, Pmax, Cout), mean and rstd (B, Pmax): all three or none (NULL:
+ * inference); zeros behind the lengths.  x_masked: NULL, or (B, Pmax, Cin) contiguous receiving x' (the weight gradient's operand).
+ * One launch, an implicit GEMM on the fp32-input MFMA; a workgroup owns 32 rows of one utterance and all Cout columns, so no
+ * utterance's result depends on another row of the batch.  Every sum has a fixed order.
+ * 1 <= B <= 65535, 1 <= Pmax <= 4096, Cin a multiple of 4 in [4, 1024], Cout a multiple of 32 in [32, 256], taps odd in [1, 9]. */
+int ttts_ragged_conv_norm_fwd(const float* x, int64_t ld_row, int64_t ld_batch, const int64_t* lens, const float* w, const float* bias,
+                              const float* gamma, const float* beta, int B, int Pmax, int Cin, int Cout, int taps, float eps,
+                              float drop_p, uint64_t seed, const uint64_t* step_seed, float* y, float* r, float* mean, float* rstd,
+                              float* x_masked /* may be NULL */, void* stream);
+/* Backward of the stage from dy (B, Pmax, Cout) contiguous (nothing behind a length is read): g = dy keep / (1 - drop_p); dgamma =
+ * sum g x_hat, dbeta = sum g; dr = LayerNorm's backward; dz = dr [r > 0]; dbias = sum dz; dw[co, ci, j] = sum dz[b, p, co] x'[b, p + j
+ * - taps / 2, ci] (ttts_conv1d_bwd_weight on dz and x_masked); dx[b, p, ci] = sum_j sum_co dz[b, p - j + taps / 2, co] w[co, ci, j] for
+ * p < pl_b, exact zeros behind it ((B, Pmax, Cin) contiguous).  dx: NULL = not wanted.  dw: NULL = not wanted (x_masked is then
+ * not read).  dw, dbias, dgamma, dbeta take `accumulate`.  ws: ttts_ragged_conv_norm_workspace_bytes(B, Pmax, Cin, Cout, taps). */
+size_t ttts_ragged_conv_norm_workspace_bytes(int B, int Pmax, int Cin, int Cout, int taps);
+int ttts_ragged_conv_norm_bwd(const float* dy, const float* r, const float* mean, const float* rstd, const float* x_masked,
+                              const int64_t* lens, const float* w, const float* gamma, int B, int Pmax, int Cin, int Cout, int taps,
+                              float drop_p, uint64_t seed, const uint64_t* step_seed, float* dx, float* dw, float* dbias,
+                              float* dgamma, float* dbeta, float* ws, size_t ws_bytes, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionW
            "evaluate_synthesis", "MelFrontEnd", "mel_filterbank", "read_wav", "normalize", "denormalize", "Vocoder", "write_wav_pcm16",
            "Resampler", "resample_table", "read_wav_native", "PitchEnergy", "phoneme_average", "length_regulate", "LengthRegulator",
            "durations_from_log", "variance_embed", "VarianceEmbedding", "variance_bins", "VarianceLoss", "VariancePredictor",
-           "VarianceAdaptor"]
+           "VarianceAdaptor", "ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -38,4 +38,7 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
                 "VarianceLoss", "VariancePredictor", "VarianceAdaptor"):   # variance adaptor of a FastSpeech-2 student (variance.py)
         from . import variance
         return getattr(variance, name)
+    if name in ("ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor"):   # the predictor on the kernels (predictor.py)
+        from . import predictor
+        return getattr(predictor, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -167,6 +167,9 @@ SIGNATURES = {
     "ttts_decode_attention_rows": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P, L, L, I, P, P]),
     "ttts_decode_attention_window": (I, [P, L, P, P, L, L, P, P, L, P, Z, I, I, I, I, P, P, L, L, I, P, P, L, P, P]),
     "ttts_mask_rows": (I, [P, P, L, I, L, L, P]),
+    "ttts_ragged_conv_norm_fwd": (I, [P, L, L, P, P, P, P, P, I, I, I, I, I, F, F, U, P, P, P, P, P, P, P]),
+    "ttts_ragged_conv_norm_workspace_bytes": (Z, [I, I, I, I, I]),
+    "ttts_ragged_conv_norm_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, U, P, P, P, P, P, P, P, Z, I, P]),
 }
 
 _lib = None

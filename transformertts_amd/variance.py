@@ -6,7 +6,7 @@ and `VarianceAdaptor`, which ties them to three predictors.  It consumes what `t
 every sum is taken in a fixed order, so the same inputs give the same bits on every call.  There is no CPU fallback.
 
 `VariancePredictor` is the one piece that is NOT on the library's kernels: a plain stock-torch module (correct, not tuned), a
-few thousand phoneme rows per batch."""
+few thousand phoneme rows per batch.  `predictor.KernelVariancePredictor` is the same module on kernels."""
 from __future__ import annotations
 
 import copy
