@@ -248,14 +248,14 @@ def oracle_loss(outputs: Dict[str, Tensor], mel: Tensor, lengths: Tensor,
     B, T, C = pred.shape
     pos = torch.arange(T).unsqueeze(0).expand(B, T)
     valid = pos < lengths.unsqueeze(1)
-    gate = (pos == (lengths.unsqueeze(1) - 1)).float()
+    gate = (pos == (lengths.unsqueeze(1) - 1)).to(stop.dtype)      # (a float32 target would make the BCE float32 whatever `stop` is)
     n = valid.sum() * C
     vm = valid.unsqueeze(-1).float()
     pred_l = (((pred - mel) ** 2) * vm).sum() / n
     post_l = (((post - mel) ** 2) * vm).sum() / n
     bce = F.binary_cross_entropy_with_logits(stop, gate, reduction="none",
-                                             pos_weight=torch.tensor(stop_weight))
-    stop_l = (bce * valid.float()).sum() / valid.sum()
+                                             pos_weight=torch.tensor(stop_weight, dtype=stop.dtype))
+    stop_l = (bce * valid.to(stop.dtype)).sum() / valid.sum()
     return {"total": pred_l + 0.5 * post_l + stop_l, "pred_mel": pred_l, "post_mel": post_l, "stop": stop_l}
 
 

@@ -704,3 +704,20 @@ def test_flat_adam_matches_torch_adam():
     for p, r in zip(ps, ref):
         assert p.data_ptr() >= opt.flat_params.data_ptr()       # still a view of the flat buffer
         assert rel_l2(p, r) < 1e-5
+    # At this rate (2.5e-7 x step) the four updates move a parameter by 1e-6 of itself: the assertion above also holds for the
+    # untouched initial parameters.  The moments do not depend on the rate: each parameter's slice of them against the reference
+    # optimizer's state, under the bounds of tests/test_hip_optim.py (tests/optim_reference.py: 4 x the stock fp32 form's error).
+    from optim_reference import BOUND
+    b = opt.bucket
+    used = torch.zeros(b.flat.numel(), dtype=torch.bool)
+    for r, off in zip(ref, b.offsets):
+        n = r.numel()
+        used[off:off + n] = True
+        st = ropt.state[r]
+        assert int(st["step"]) == opt._step == 4
+        assert rel_l2(opt.exp_avg[off:off + n], st["exp_avg"].reshape(-1)) < BOUND["exp_avg"]
+        assert rel_l2(opt.exp_avg_sq[off:off + n], st["exp_avg_sq"].reshape(-1)) < BOUND["exp_avg_sq"]
+    # the padding between the 64-float aligned slices stays exactly zero in parameters and moments
+    assert int((~used).sum()) > 0
+    for buf in (opt.flat_params, opt.exp_avg, opt.exp_avg_sq):
+        assert float(buf.cpu()[~used].abs().max()) == 0.0

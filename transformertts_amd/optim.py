@@ -83,8 +83,10 @@ class FlatAdam(torch.optim.Optimizer):
         return d
 
     def load_state_dict(self, state_dict):
-        flat = state_dict.pop("flat", None)
-        super().load_state_dict(state_dict)
+        # the caller's dictionary is left as it was (torch.optim.Optimizer.load_state_dict does not mutate its argument either):
+        # the same checkpoint loads a second time, into this optimizer or another, with its step count and moments
+        flat = state_dict.get("flat")
+        super().load_state_dict({k: v for k, v in state_dict.items() if k != "flat"})
         if flat is not None:
             self._step = int(flat["step"])
             self.exp_avg.copy_(flat["exp_avg"])
