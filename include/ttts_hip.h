@@ -1040,6 +1040,32 @@ int ttts_ragged_conv_norm_bwd(const float* dy, const float* r, const float* mean
                               float drop_p, uint64_t seed, const uint64_t* step_seed, float* dx, float* dw, float* dbias,
                               float* dgamma, float* dbeta, float* ws, size_t ws_bytes, int accumulate, void* stream);
 
+/* ---- additive (ABI 24): the conv feed-forward sublayer of an FFT block on ragged rows (predictor.hip) ---------
+ * FastSpeech's position-wise feed-forward: two Conv1d layers, dropout on the branch, residual, LayerNorm.  x (B, Pmax, D) through
+ * (ld_row, ld_batch); pl_b and x' as above; w1 (Chid, D, k1), b1, w2 (D, Chid, k2), b2 as nn.Conv1d holds them.
+ *   h = max(conv_k1(x') + b1, 0)   (B, Pmax, Chid), exact zeros behind pl_b; required (the second launch reads it)
+ *   z = conv_k2(h) + b2;  s = x' + z keep_elem(seed ^ *step_seed, flat index in (B, Pmax, D)) / (1 - drop_p)  (no multiply at drop_p 0)
+ *   y = ((s - mean) rstd) gamma + beta over D (biased variance, two passes), exact zeros behind pl_b
+ * Two launches of the stage's implicit GEMM: bias + ReLU in column blocks of 256, then bias + dropout + residual + LayerNorm with a
+ * workgroup owning whole rows (the residual is read in the epilogue through x's strides, below the length only).  s (B, Pmax, D),
+ * mean and rstd (B, Pmax): all three or none (NULL: inference).  x_masked: NULL, or (B, Pmax, D) contiguous receiving x'.
+ * D a multiple of 32 in [32, 256], Chid a multiple of 32 in [32, 1024], k1 and k2 odd in [1, 9], Pmax <= 4096, B <= 65535. */
+int ttts_ragged_conv_ffn_fwd(const float* x, int64_t ld_row, int64_t ld_batch, const int64_t* lens, const float* w1, const float* b1,
+                             const float* w2, const float* b2, const float* gamma, const float* beta, int B, int Pmax, int D, int Chid,
+                             int k1, int k2, float eps, float drop_p, uint64_t seed, const uint64_t* step_seed, float* h, float* y,
+                             float* s, float* mean, float* rstd, float* x_masked /* may be NULL */, void* stream);
+/* Backward of the sublayer from dy (B, Pmax, D) contiguous (nothing behind a length is read): ds = LayerNorm's backward (also the
+ * residual's share of dx), dgamma = sum dy x_hat, dbeta = sum dy; dz2 = ds keep / (1 - drop_p); dz1 = conv(dz2, flipped w2) [h > 0];
+ * dx = conv(dz1, flipped w1) + ds, exact zeros behind the lengths; dw2, db2 = ttts_conv1d_bwd_weight(dz2, h); dw1, db1 =
+ * ttts_conv1d_bwd_weight(dz1, x_masked).  dx: NULL = not wanted.  dw1, db1, dw2, db2: all four or none (NULL: not wanted; x_masked is
+ * then not read).  The six parameter gradients take `accumulate`.  ws: ttts_ragged_conv_ffn_workspace_bytes(B, Pmax, D, Chid, k1, k2). */
+size_t ttts_ragged_conv_ffn_workspace_bytes(int B, int Pmax, int D, int Chid, int k1, int k2);
+int ttts_ragged_conv_ffn_bwd(const float* dy, const float* s, const float* mean, const float* rstd, const float* h, const float* x_masked,
+                             const int64_t* lens, const float* w1, const float* w2, const float* gamma, int B, int Pmax, int D, int Chid,
+                             int k1, int k2, float drop_p, uint64_t seed, const uint64_t* step_seed, float* dx, float* dw1, float* db1,
+                             float* dw2, float* db2, float* dgamma, float* dbeta, float* ws, size_t ws_bytes, int accumulate,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

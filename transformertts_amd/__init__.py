@@ -9,7 +9,8 @@ __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionW
            "evaluate_synthesis", "MelFrontEnd", "mel_filterbank", "read_wav", "normalize", "denormalize", "Vocoder", "write_wav_pcm16",
            "Resampler", "resample_table", "read_wav_native", "PitchEnergy", "phoneme_average", "length_regulate", "LengthRegulator",
            "durations_from_log", "variance_embed", "VarianceEmbedding", "variance_bins", "VarianceLoss", "VariancePredictor",
-           "VarianceAdaptor", "ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor"]
+           "VarianceAdaptor", "ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor", "ragged_conv_ffn", "ConvFeedForward",
+           "FFTBlock", "FFTStack", "FastSpeech2Student"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -41,4 +42,7 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
     if name in ("ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor"):   # the predictor on the kernels (predictor.py)
         from . import predictor
         return getattr(predictor, name)
+    if name in ("ragged_conv_ffn", "ConvFeedForward", "FFTBlock", "FFTStack", "FastSpeech2Student"):   # FFT blocks, the student (fft.py)
+        from . import fft
+        return getattr(fft, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -170,6 +170,9 @@ SIGNATURES = {
     "ttts_ragged_conv_norm_fwd": (I, [P, L, L, P, P, P, P, P, I, I, I, I, I, F, F, U, P, P, P, P, P, P, P]),
     "ttts_ragged_conv_norm_workspace_bytes": (Z, [I, I, I, I, I]),
     "ttts_ragged_conv_norm_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, U, P, P, P, P, P, P, P, Z, I, P]),
+    "ttts_ragged_conv_ffn_fwd": (I, [P, L, L, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, U, P, P, P, P, P, P, P, P]),
+    "ttts_ragged_conv_ffn_workspace_bytes": (Z, [I, I, I, I, I, I]),
+    "ttts_ragged_conv_ffn_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, U, P, P, P, P, P, P, P, P, P, Z, I, P]),
 }
 
 _lib = None
