@@ -796,6 +796,39 @@ int ttts_variance_loss_fwd(const float* log_d_pred, const int64_t* durations, co
 int ttts_variance_loss_bwd(const float* log_d_pred, const int64_t* durations, const float* pitch_pred, const float* pitch_target,
                            const float* energy_pred, const float* energy_target, const int64_t* phoneme_lens, int B, int Pmax, float w_d,
                            float w_p, float w_e, const float* gout, float* d_log_d, float* d_pitch, float* d_energy, void* stream);
+/* ---- mel loss of the student (csrc/student_loss.hip; additive, the ABI version stays 24) --------------------------------
+ * The masked mean absolute and mean squared error between two ragged mel batches.  pred is (B, T, M) fp32 read through
+ * (ld_row_pred, ld_batch_pred), target (B, Tt, M) through its own pair -- the float4-row rule of the variance entries: rows of
+ * M floats a multiple of 4 floats apart, utterances a multiple of 4 floats apart that cover T resp. Tt rows, 16-byte aligned
+ * bases.  pred_lens, target_lens: (B,) int64 on the device.
+ *   n_b = clamp(min(pred_lens[b], target_lens[b]), 0, min(T, Tt)); N = sum_b n_b; den = (float)(N M)
+ *   out[0] mae = sum |pred - target| / den, out[1] mse = sum (pred - target)^2 / den over b, t < n_b, m; both exactly 0 when N = 0
+ *   out[2] mel = w_mae mae + w_mse mse; out[3] total = mel + extra[0] (extra NULL: mel itself); frames[0] = N
+ * ttts_mel_loss_fwd is two launches: partial sums per workgroup into `workspace` (ttts_mel_loss_workspace_bytes; utterances are
+ * cut into chunks of ttts_mel_loss_rows() frames, min(B ceil(min(T, Tt) / rows), ttts_mel_loss_max_workgroups()) workgroups
+ * stride over the chunks -- the grid follows from the shapes alone), then one workgroup of ttts_mel_loss_sweep() threads that
+ * adds the partials in ascending order and takes N as an integer sum.  The order of every sum is stated at the top of the
+ * source file.  ttts_mel_loss_bwd is one element-wise launch: with the upstream gradients of the four outputs as device scalars
+ * (NULL counts as 0), G = g_total + g_mel, dpred[b, t, m] = sign(d) ((G w_mae + g_mae) / den) + ((2 (G w_mse + g_mse)) / den) d
+ * for t < n_b with d = pred - target and sign(0) = 0; dpred is (B, T, M) contiguous and holds exact zeros at and behind n_b,
+ * and everywhere when N = 0.  The gradient of extra is g_total (the caller's).
+ * No atomics, no allocation, no host read, the same bits on every call, capturable; nothing at or behind n_b is read in either
+ * operand.  Refused before any launch, with a message that names the value: null required pointers, B outside [1, 65535], T or Tt
+ * outside [1, 2^20], M outside [4, 4096] or no multiple of 4, strides that do not cover a row or are no multiple of 4,
+ * misaligned pointers, a workspace that is too small, weights that are not finite.  ttts_mel_loss_workspace_bytes returns 0 for
+ * a shape the entries refuse. */
+int ttts_mel_loss_rows(void);
+int ttts_mel_loss_sweep(void);
+int ttts_mel_loss_max_workgroups(void);
+size_t ttts_mel_loss_workspace_bytes(int B, int T, int Tt, int M);
+int ttts_mel_loss_fwd(const float* pred, int64_t ld_row_pred, int64_t ld_batch_pred, const float* target, int64_t ld_row_target,
+                      int64_t ld_batch_target, const int64_t* pred_lens, const int64_t* target_lens, int B, int T, int Tt, int M,
+                      float w_mae, float w_mse, const float* extra, float* out, int64_t* frames, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int ttts_mel_loss_bwd(const float* pred, int64_t ld_row_pred, int64_t ld_batch_pred, const float* target, int64_t ld_row_target,
+                      int64_t ld_batch_target, const int64_t* pred_lens, const int64_t* target_lens, int B, int T, int Tt, int M,
+                      float w_mae, float w_mse, const float* g_mae, const float* g_mse, const float* g_mel, const float* g_total,
+                      float* dpred, void* stream);
 /* ttts_heads_pad / ttts_heads_unpad with the padded width as an argument (ABI v17): width 64 (head_dim 1 .. 64) or 128
  * (head_dim 1 .. 128); dst resp. src is (rows, H*width).  The operands of the attention call sites above when head_dim is not
  * the kernels' own width. */

@@ -10,7 +10,8 @@ __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionW
            "Resampler", "resample_table", "read_wav_native", "PitchEnergy", "phoneme_average", "length_regulate", "LengthRegulator",
            "durations_from_log", "variance_embed", "VarianceEmbedding", "variance_bins", "VarianceLoss", "VariancePredictor",
            "VarianceAdaptor", "ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor", "ragged_conv_ffn", "ConvFeedForward",
-           "FFTBlock", "FFTStack", "FastSpeech2Student"]
+           "FFTBlock", "FFTStack", "FastSpeech2Student", "mel_loss", "FastSpeech2Loss", "StudentTrainStep", "distillation_targets",
+           "synth_student_batch"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -45,4 +46,10 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
     if name in ("ragged_conv_ffn", "ConvFeedForward", "FFTBlock", "FFTStack", "FastSpeech2Student"):   # FFT blocks, the student (fft.py)
         from . import fft
         return getattr(fft, name)
+    if name in ("mel_loss", "FastSpeech2Loss", "StudentTrainStep", "distillation_targets"):   # training the student (student.py)
+        from . import student
+        return getattr(student, name)
+    if name == "synth_student_batch":   # a synthetic batch with the student's seven keys (workload.py)
+        from . import workload
+        return workload.synth_student_batch
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

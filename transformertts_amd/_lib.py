@@ -123,6 +123,12 @@ SIGNATURES = {
     "ttts_variance_embed_fwd": (I, [P, L, L, P, P, P, I, P, I, P, P, P, I, I, I, P, P, P, P]),
     "ttts_variance_loss_fwd": (I, [P, P, P, P, P, P, P, I, I, F, F, F, P, P]),
     "ttts_variance_loss_bwd": (I, [P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P]),
+    "ttts_mel_loss_rows": (I, []),
+    "ttts_mel_loss_sweep": (I, []),
+    "ttts_mel_loss_max_workgroups": (I, []),
+    "ttts_mel_loss_workspace_bytes": (Z, [I, I, I, I]),
+    "ttts_mel_loss_fwd": (I, [P, L, L, P, L, L, P, P, I, I, I, I, F, F, P, P, P, P, Z, P]),
+    "ttts_mel_loss_bwd": (I, [P, L, L, P, L, L, P, P, I, I, I, I, F, F, P, P, P, P, P, P]),
     "ttts_heads_pad": (I, [P, L, P, L, I, I, P]),
     "ttts_heads_unpad": (I, [P, P, L, L, I, I, P]),
     "ttts_heads_pad_w": (I, [P, L, P, L, I, I, I, P]),

@@ -62,3 +62,32 @@ def synth_batch(B: int, Tp: int = 100, Tm: int = 870, n_mels: int = 80, n_phon: 
     mel = mel * (torch.arange(tm).unsqueeze(0) < ml.unsqueeze(1)).unsqueeze(-1)
     return {"phoneme": ph.contiguous(), "melspec": mel.contiguous(), "phoneme_lens": pl.contiguous(),
             "melspec_lens": ml.contiguous()}
+
+
+def synth_student_batch(B: int, Tp: int = 110, n_mels: int = 80, n_vocab: int = 100, max_duration: int = 15, ragged: bool = False,
+                        seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """A CPU batch with the seven keys `StudentTrainStep` takes.  Every valid phoneme lasts 1 .. max_duration frames (uniform), so
+    sum(durations[b, :phoneme_lens[b]]) == melspec_lens[b] and the mel is padded to the longest sum; pitch is uniform in [70, 500)
+    Hz and energy in [0, 1) (inside the default boundaries of `VarianceEmbedding`), ids are in [1, n_vocab).  Dense: every utterance
+    has Tp phonemes.  Ragged: phoneme counts uniform in [min(8, Tp), Tp] with utterance 0 at Tp, rows sorted by phoneme count
+    descending.  Behind a length everything is 0."""
+    if min(B, Tp, n_mels, max_duration) < 1 or n_vocab < 2:
+        raise ValueError(f"synth_student_batch: B, Tp, n_mels, max_duration must be positive and n_vocab at least 2, got {B}, {Tp}, "
+                         f"{n_mels}, {max_duration}, {n_vocab}")
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    pl = torch.full((B,), Tp, dtype=torch.long)
+    if ragged:
+        pl = torch.randint(min(8, Tp), Tp + 1, (B,), generator=g, dtype=torch.long)
+        pl[0] = Tp
+        pl = pl[torch.argsort(pl, descending=True, stable=True)]
+    valid = torch.arange(Tp).unsqueeze(0) < pl.unsqueeze(1)
+    ph = torch.randint(1, n_vocab, (B, Tp), generator=g, dtype=torch.long) * valid
+    dur = torch.randint(1, max_duration + 1, (B, Tp), generator=g, dtype=torch.long) * valid
+    pitch = (70.0 + 430.0 * torch.rand(B, Tp, generator=g)) * valid
+    energy = torch.rand(B, Tp, generator=g) * valid
+    ml = dur.sum(1)
+    tm = int(ml.max())
+    mel = torch.randn(B, tm, n_mels, generator=g) * (torch.arange(tm).unsqueeze(0) < ml.unsqueeze(1)).unsqueeze(-1)
+    return {"phoneme": ph.contiguous(), "phoneme_lens": pl.contiguous(), "melspec": mel.contiguous(), "melspec_lens": ml.contiguous(),
+            "durations": dur.contiguous(), "pitch": pitch.contiguous(), "energy": energy.contiguous()}
