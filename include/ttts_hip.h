@@ -1099,6 +1099,28 @@ int ttts_ragged_conv_ffn_bwd(const float* dy, const float* s, const float* mean,
                              float* dw2, float* db2, float* dgamma, float* dbeta, float* ws, size_t ws_bytes, int accumulate,
                              void* stream);
 
+/* ---- additive (ABI 24): the layers of a HiFi-GAN generator on ragged rows, inference only (hifigan.hip) ---------
+ * Activations are (B, Nmax, C) fp32, contiguous; pl_b = clamp(lens[b], 0, Nmax); rows at or behind pl_b count as zeros for the taps,
+ * are never read (a NaN there does not leak) and come back as exact zeros, so every utterance is convolved as if it were alone,
+ * zero-padded at its own ends.  Every sum has a fixed order; no atomics, no allocation, no host read.
+ * The dilated convolution, an implicit GEMM on the fp32-input MFMA:
+ *   z[b, n, co] = sum_j sum_ci w[j, ci, co] f(x[b, n + (j - taps / 2) dilation, ci]);  f = leaky_relu(., in_slope), in_slope = 1: none
+ *   v = z + bias[co] + residual[b, n, co]   (bias, residual: NULL = absent; residual (B, Nmax, Cout), read below the length only)
+ *   y = v (NULL: not wanted);  acc_mode 1: acc = v acc_scale;  acc_mode 2: acc = (acc + v) acc_scale;  acc_mode 0: acc must be NULL
+ * w is the convolution's weight re-laid to (taps, Cin, Cout).  A ConvTranspose1d with stride u and u <= k <= 2 u taps is this entry
+ * with 3 taps onto u Cout columns: (B, T, u Cout) row-major is (B, T u, Cout) row-major.  The reduction runs over chunks of 32 input
+ * channels, inside a chunk over the taps; the fma chain is closed after every (chunk, tap) and the sums are added in that order.
+ * Cin a multiple of 32 in [32, 512] or a multiple of 4 in [4, 128]; Cout a multiple of 32 in [32, 2048]; taps odd in [1, 11];
+ * dilation in [1, 12]; Nmax <= 2^21; B <= 65535; every operand at most the bytes the query below returns. */
+int ttts_hifigan_max_operand_bytes(void);
+int ttts_hifigan_conv(const float* x, const int64_t* lens, const float* w, const float* bias, const float* residual, float* y,
+                      float* acc, int B, int Nmax, int Cin, int Cout, int taps, int dilation, float in_slope, int acc_mode,
+                      float acc_scale, void* stream);
+/* y[b, n] = tanh(bias[0] + sum_j sum_ci w[j, ci] leaky_relu(x[b, n + j - taps / 2, ci], in_slope)) for n < pl_b, exact zeros behind
+ * it: a generator's last layer, one output per row on the VALU.  w (taps, Cin); y (B, Nmax).  Cin a multiple of 32 in [32, 512]. */
+int ttts_hifigan_post(const float* x, const int64_t* lens, const float* w, const float* bias, float* y, int B, int Nmax, int Cin,
+                      int taps, float in_slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ __all__ = ["model", "ops", "extract_durations", "teacher_durations", "AttentionW
            "durations_from_log", "variance_embed", "VarianceEmbedding", "variance_bins", "VarianceLoss", "VariancePredictor",
            "VarianceAdaptor", "ragged_conv_norm", "RaggedConvNorm", "KernelVariancePredictor", "ragged_conv_ffn", "ConvFeedForward",
            "FFTBlock", "FFTStack", "FastSpeech2Student", "mel_loss", "FastSpeech2Loss", "StudentTrainStep", "distillation_targets",
-           "synth_student_batch"]
+           "synth_student_batch", "HiFiGANConfig", "HiFiGANGenerator", "fold_weight_norm", "transposed_as_conv", "ragged_dilated_conv",
+           "load_hifigan"]
 
 
 def __getattr__(name):          # the two calls of alignment.py, imported (and torch with them) when first asked for
@@ -52,4 +53,8 @@ def __getattr__(name):          # the two calls of alignment.py, imported (and t
     if name == "synth_student_batch":   # a synthetic batch with the student's seven keys (workload.py)
         from . import workload
         return workload.synth_student_batch
+    if name in ("HiFiGANConfig", "HiFiGANGenerator", "fold_weight_norm", "transposed_as_conv", "ragged_dilated_conv",
+                "load_hifigan"):   # the HiFi-GAN generator on the kernels (hifigan.py)
+        from . import hifigan
+        return getattr(hifigan, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -179,6 +179,9 @@ SIGNATURES = {
     "ttts_ragged_conv_ffn_fwd": (I, [P, L, L, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, U, P, P, P, P, P, P, P, P]),
     "ttts_ragged_conv_ffn_workspace_bytes": (Z, [I, I, I, I, I, I]),
     "ttts_ragged_conv_ffn_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, U, P, P, P, P, P, P, P, P, P, Z, I, P]),
+    "ttts_hifigan_max_operand_bytes": (I, []),
+    "ttts_hifigan_conv": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, F, P]),
+    "ttts_hifigan_post": (I, [P, P, P, P, P, I, I, I, I, F, P]),
 }
 
 _lib = None
